@@ -9,15 +9,18 @@ One "step" = one pass of the sparse hot path over one batch of B ids already res
 sides.  With --gpus N > 1 (launched by torch.distributed.run) every rank feeds its own B ids and the
 table is sharded by fid mod N with four all-to-alls per step over RCCL (weak scaling).
 
-Contract: prints ONE JSON line on rank 0.  Extra objects: `roofline` (dominant kernel, HIP-event
-timed on the launch stream), `cpu_baseline` (reference map + AVX Adagrad built from the reference's
-own sources, oracle/_ref, timed on this box's host cores; N=1 only).
+Contract: prints ONE JSON line on rank 0; a plain run sets up, warms up, times exactly --steps steps
+and prints it.  --dump-outputs DIR writes the embeddings the last timed step returned.  With --full,
+extra objects: `roofline` (dominant kernel, HIP-event timed on the launch stream), `cpu_baseline`
+(reference map + AVX Adagrad built from the reference's own sources, oracle/_ref, timed on this box's
+host cores; N=1 only), `parity_check`, and the other launch modes' windows.
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -34,6 +37,11 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable copy
 PROBE_BYTES = 72        # keys+tags of both candidate buckets
+DUMP_LIMIT = 64 << 20   # --dump-outputs: bytes of all files together
+RING = 1440             # distinct batches of a plain run at most (ring_size): a multiple of 60 = whole graph chunks
+                        # of 10 steps and whole turns of the 2- and 3-slot dedup rotation (a replayed lap of graphs
+                        # comes back to the state it was captured from)
+RING_DLRM = 300         # the same for --config dlrm26 (26 tables: 13.6 MB of ids per step)
 
 
 def parse():
@@ -112,7 +120,20 @@ def parse():
                  help="write a per-wavefront timeline (.npz) of three pipelined steps")
   p.add_argument("--no-stage-timing", action="store_true",
                  help="skip the per-kernel HIP-event pass (profiling the overlapped step only)")
-  return p.parse_args()
+  p.add_argument("--full", action="store_true",
+                 help="everything beyond the headline as well: the other launch modes' windows (eager, eager_cpp, "
+                      "exact_order, the 200-step reference window), the per-kernel HIP-event pass and roofline, "
+                      "the parity check against the oracle and the CPU baseline (each still switched off by its "
+                      "--no-* option).  Without it a run sets up, warms up, times --steps steps and prints the line")
+  p.add_argument("--dump-outputs", default="", metavar="DIR",
+                 help="after the timed steps, write the embeddings the last timed step's forward returned as "
+                      "DIR/<name>.npy (float32; a fixed seeded sample of rows beyond %d MB in all)" % (DUMP_LIMIT >> 20))
+  args = p.parse_args()
+  if args.trace_out and not args.full:
+    p.error("--trace-out rides in the per-kernel pass: it needs --full")
+  if not args.full:
+    args.no_cpu_baseline = args.no_extra_windows = args.no_parity_check = args.no_stage_timing = True
+  return args
 
 
 def algorithmic_bytes(B, U, D, S):
@@ -257,6 +278,58 @@ def parity_numbers(got, exp):
           "rel_floor": 1e-6}
 
 
+def ring_size(n_batches, K, full, ring):
+  """Distinct batches of the stream (step s trains batch s mod P).  --full keeps every batch fresh, as each of
+  its passes assumes, unless --steps alone passes the ring; a plain run needs n_batches for its own steps only,
+  and beyond `ring` its batches come round again (the set-up does not grow with --steps)."""
+  return n_batches if (full and K <= ring) else min(n_batches, ring)
+
+
+def ring_stretches(lo, hi, P):
+  """Steps [lo, hi) of a ring of P batches for a loop that reads batch b + 1 ahead of batch b within the ring
+  (the C loop, csrc/eager_loop.c): [(first batch, steps)] stretches that end one step short of the ring's end,
+  and (batch P - 1, None) for the step whose next batch is the ring's first, enqueued one by one."""
+  out, s = [], lo
+  while s < hi:
+    b = s % P
+    e = min(hi, s + (P - 1 - b))
+    if e > s:
+      out.append((b, e - s))
+    if e < hi:
+      out.append((e % P, None))
+      e += 1
+    s = e
+  return out
+
+
+def repeated_steps(lo, hi, P):
+  """Steps of [lo, hi) that train a batch an earlier step of the run trained (s >= P)."""
+  return max(0, hi - max(lo, P))
+
+
+def take_outputs(arrays, limit=DUMP_LIMIT):
+  """--dump-outputs: host float32 copies of `arrays` ({name: device tensor, rows first}) taken right after the
+  timed window, before anything else overwrites the buffers.  Beyond `limit` bytes in all, every array keeps
+  the same fraction of its rows, chosen by a fixed seed: the sample depends on the shapes only."""
+  import torch
+  total = sum(4 * t.numel() for t in arrays.values())
+  out = {}
+  for name, t in arrays.items():
+    if total > limit:
+      n = t.shape[0]
+      keep = max(1, int(n * (limit / total)))
+      rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+      t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+    out[name] = t.float().cpu().numpy()
+  return out
+
+
+def write_outputs(d, outs):
+  os.makedirs(d, exist_ok=True)
+  for name, a in outs.items():
+    np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main_dlrm(args):
   """BASELINE.json configs[4]'s shape on ONE MI355X (the 8-GPU sharding of it is the driver's
   --gpus run of the default config): T feature tables of dims 16 / 32 / 64 (fused Adagrad), B
@@ -278,12 +351,13 @@ def main_dlrm(args):
   dcyc = [int(x) for x in args.dims.split(",")]
   dims = [dcyc[i % len(dcyc)] for i in range(T)]
   names = ["f%02d" % (i + 1) for i in range(T)]    # sorted order == slot order
-  reps = min(K, 50)
+  reps = min(K, 50) if not args.no_stage_timing else 0
   n_steps = W + K + reps + 4
+  P = ring_size(n_steps + 1, K, args.full, RING_DLRM)   # distinct ragged batches: step s trains batch s mod P
   lr = 0.001
   configs = {}
   for i, n in enumerate(names):
-    rows_cap = resident + n_steps * 24000 + (1 << 16)   # ~13 k distinct ids per batch, < 40 % new
+    rows_cap = resident + P * 24000 + (1 << 16)   # ~13 k distinct ids per batch, < 40 % new
     slots = 4
     while slots * 0.5 < rows_cap:
       slots *= 2
@@ -318,12 +392,15 @@ def main_dlrm(args):
   # ---- inputs resident in HBM: one ragged batch per step (tables in slot order), two gradient
   # buffers of sum(B * dim) floats each (2 x 247 MB at 26 tables: beyond the 256 MiB LLC)
   splits = np.arange(T + 1, dtype=np.int64) * B
-  ids_host = np.empty((n_steps + 1, T * B), dtype=np.int64)
-  for s in range(n_steps + 1):
+  ids_host = np.empty((P, T * B), dtype=np.int64)
+
+  def fill(s):
     for i in range(T):
       ids_host[s, i * B:(i + 1) * B] = S.id_batch(s * 64 + i + 1, B, V, "zipf", feature_slot=i + 1)
+  with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
+    list(ex.map(fill, range(P)))
   ids_all = torch.from_numpy(ids_host).to(dev)
-  rag = [Ragged(ids_all[s], splits) for s in range(n_steps + 1)]
+  rag = [Ragged(ids_all[s], splits) for s in range(P)]
   gsz = B * sum(dims)
   goff = np.concatenate([[0], np.cumsum([B * d for d in dims])])
 
@@ -470,12 +547,13 @@ def main_dlrm(args):
 
   def run(lo, hi):
     for s in range(lo, hi):
-      step.forward(rag[s], rag[s + 1], out=out)
+      b = s % P
+      step.forward(rag[b], rag[(s + 1) % P], out=out)
       if dense is not None:
         step.backward(dense_step(out), ut(s))
       else:
-        step.backward(grad_pool[s % NG], ut(s))
-        applied.append((s, s % NG, ut(s)))
+        step.backward(grad_pool[b % NG], ut(s))
+        applied.append((b, b % NG, ut(s)))
       if args.evict_every and (s + 1) % args.evict_every == 0:
         for n in names:
           mt.evict(n)
@@ -492,60 +570,67 @@ def main_dlrm(args):
   torch.cuda.synchronize()
   elapsed = time.perf_counter() - t
   gc.enable()
+  if args.dump_outputs:   # the step's flat output, one view per table
+    outputs = take_outputs({"embeddings_" + n: out[goff[i]:goff[i + 1]].view(B, dims[i])
+                            for i, n in enumerate(names)})
 
   # ---- per-kernel timing: HIP events with the kernels' own begin/end (mhte_profile_arm) ----
-  acc, uniq = {}, []
-  _lib.profile_arm(8 * reps)
-  for s in range(W + K, W + K + reps):
-    step.forward(rag[s], rag[s + 1], out=out)
-    if s % 10 == 0:
-      uniq.append(step.unique_counts())
-    if dense is not None:
-      step.backward(dense_step(out), ut(s))
-    else:
-      step.backward(grad_pool[s % NG], ut(s))
-      applied.append((s, s % NG, ut(s)))
-  torch.cuda.synchronize()
-  for name, us in _lib.profile_read():
-    a = acc.setdefault(name, [0, 0.0])
-    a[0] += 1
-    a[1] += us
-  U = np.mean(np.stack(uniq), axis=0)              # distinct ids per table and batch
-  alg_fwd = alg_bwd = 0
-  for i in range(T):
-    _, pk = algorithmic_bytes(B, float(U[i]), dims[i], dims[i])
-    alg_fwd += pk["lookup_kernel"]
-    alg_bwd += pk["sum_apply_kernel"]
-  alg = {"mstep_fwd_kernel": alg_fwd, "mstep_bwd_kernel": alg_bwd}
-  if sharded:
-    alg = {}
+  # (--full: a pass of its own behind the timed region)
+  roofline, stages, U = None, {}, None
+  if reps:
+    acc, uniq = {}, []
+    _lib.profile_arm(8 * reps)
+    for s in range(W + K, W + K + reps):
+      b = s % P
+      step.forward(rag[b], rag[(s + 1) % P], out=out)
+      if s % 10 == 0:
+        uniq.append(step.unique_counts())
+      if dense is not None:
+        step.backward(dense_step(out), ut(s))
+      else:
+        step.backward(grad_pool[b % NG], ut(s))
+        applied.append((b, b % NG, ut(s)))
+    torch.cuda.synchronize()
+    for name, us in _lib.profile_read():
+      a = acc.setdefault(name, [0, 0.0])
+      a[0] += 1
+      a[1] += us
+    U = np.mean(np.stack(uniq), axis=0)              # distinct ids per table and batch
+    alg_fwd = alg_bwd = 0
     for i in range(T):
-      for k, v in sharded_algorithmic_bytes(B, float(U[i]), dims[i], dims[i]).items():
-        alg[k] = alg.get(k, 0) + v
-    alg.pop("dd_kernels")
-  stages = {}
-  for name, (cnt, tot) in sorted(acc.items()):
-    stages[name] = {"avg_us": round(tot / cnt, 2), "launches_per_step": round(cnt / reps, 2)}
-    if name in alg:
-      stages[name]["alg_bytes"] = int(alg[name])
-      stages[name]["GBps"] = round(alg[name] / (tot / cnt) / 1e3, 1)
-  dom = max((k for k in stages if k in alg), key=lambda k: stages[k]["avg_us"])
-  a_gbps = alg[dom] / stages[dom]["avg_us"] / 1e3
-  step_bytes = alg_fwd + alg_bwd
-  # (the committed PMC passes are of the default 26 x 65 536 shape)
-  traffic, traffic_src = pmc_traffic(dom) if (T == 26 and B == 65536 and not sharded) else (None, None)
-  roofline = {"bound": "hbm", "kernel": dom, "achieved": round(a_gbps, 1), "peak": HBM_PEAK_GBPS,
-              "unit": "GB/s", "frac": round(a_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
-              "traffic_source": traffic_src,
-              "alg_bytes_per_launch": int(alg[dom]), "avg_launch_us": stages[dom]["avg_us"],
-              "timing": "hipExtLaunchKernelGGL start/stop events on the launch stream, %d launches" % reps,
-              "step_alg_bytes": int(step_bytes),
-              "step_GBps": round(step_bytes / (elapsed / K) / 1e9, 1),
-              "step_frac": round(step_bytes / (elapsed / K) / 1e9 / HBM_PEAK_GBPS, 4)}
+      _, pk = algorithmic_bytes(B, float(U[i]), dims[i], dims[i])
+      alg_fwd += pk["lookup_kernel"]
+      alg_bwd += pk["sum_apply_kernel"]
+    alg = {"mstep_fwd_kernel": alg_fwd, "mstep_bwd_kernel": alg_bwd}
+    if sharded:
+      alg = {}
+      for i in range(T):
+        for k, v in sharded_algorithmic_bytes(B, float(U[i]), dims[i], dims[i]).items():
+          alg[k] = alg.get(k, 0) + v
+      alg.pop("dd_kernels")
+    stages = {}
+    for name, (cnt, tot) in sorted(acc.items()):
+      stages[name] = {"avg_us": round(tot / cnt, 2), "launches_per_step": round(cnt / reps, 2)}
+      if name in alg:
+        stages[name]["alg_bytes"] = int(alg[name])
+        stages[name]["GBps"] = round(alg[name] / (tot / cnt) / 1e3, 1)
+    dom = max((k for k in stages if k in alg), key=lambda k: stages[k]["avg_us"])
+    a_gbps = alg[dom] / stages[dom]["avg_us"] / 1e3
+    step_bytes = alg_fwd + alg_bwd
+    # (the committed PMC passes are of the default 26 x 65 536 shape)
+    traffic, traffic_src = pmc_traffic(dom) if (T == 26 and B == 65536 and not sharded) else (None, None)
+    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(a_gbps, 1), "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": round(a_gbps / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "alg_bytes_per_launch": int(alg[dom]), "avg_launch_us": stages[dom]["avg_us"],
+                "timing": "hipExtLaunchKernelGGL start/stop events on the launch stream, %d launches" % reps,
+                "step_alg_bytes": int(step_bytes),
+                "step_GBps": round(step_bytes / (elapsed / K) / 1e9, 1),
+                "step_frac": round(step_bytes / (elapsed / K) / 1e9 / HBM_PEAK_GBPS, 4)}
 
   # ---- parity of the benched state against the oracle's replay, three tables (one per dim) ----
   parity = None
-  if dense is not None:
+  if dense is not None and args.full:
     # the dense leg alone, timed with events on its stream: MFMA roofline of the GEMMs
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -615,7 +700,7 @@ def main_dlrm(args):
         times = []
         for s in range(5 + 30):
           tt = time.perf_counter()
-          ps.step(ids_host[s, i * B:(i + 1) * B], gh, lr, ut(s), want_emb=True)
+          ps.step(ids_host[s % P, i * B:(i + 1) * B], gh, lr, ut(s), want_emb=True)
           times.append(time.perf_counter() - tt)
         per_dim[d] = float(np.median(times[5:]))
       t_step = sum(per_dim[d] for d in dims)
@@ -650,7 +735,9 @@ def main_dlrm(args):
                         if sharded else "")),
           "tables": T, "dims": dims, "batch_per_table": B, "universe_per_table": V,
           "resident_rows_start": int(sum(size0)), "resident_rows_end": int(sum(size1)),
-          "unique_ids_per_batch_mean": float(U.mean()), "eviction_scans_in_timed_region": evictions[0],
+          "unique_ids_per_batch_mean": None if U is None else float(U.mean()),
+          "eviction_scans_in_timed_region": evictions[0], "distinct_batches": P,
+          "timed_steps_on_repeated_batches": repeated_steps(W, W + K, P),
           "gradient_bytes_rotated": int(NG * gsz * 4), "prefill_s": round(prefill_s, 2),
           "update_time": "one second per %d steps" % sps,
           "launch": "eager",
@@ -662,6 +749,8 @@ def main_dlrm(args):
   }
   if cpu and cpu.get("value"):
     out_json["vs_cpu_baseline"] = round(value / cpu["value"], 2)
+  if args.dump_outputs:
+    write_outputs(args.dump_outputs, outputs)
   emit_line(out_json)
 
 
@@ -744,8 +833,39 @@ def main():
   S_state = D if args.opt == "adagrad" else 0
   resident = int(args.resident_rows)
 
+  # ---- inputs resident in HBM before the timed region ----
+  # Every launch mode trains FRESH batches (a replay of batches the table has already seen would
+  # find every id resident and skip the insert path).  The modes run back to back over one
+  # contiguous batch sequence: the last step of a mode deduplicates the first batch of the next
+  # mode ahead, exactly as it does inside a mode.  The sequence is a ring of P batches (ring_size):
+  # step s trains batch s mod P with gradient buffer (s mod P) mod NG at update_time(s mod P).  --full
+  # gets a fresh batch for every step unless --steps alone passes RING; a plain run's batches come
+  # round again beyond RING, so that its set-up does not grow with --steps, and the line says how
+  # many timed steps trained a repeated batch.
+  # launches of the per-kernel timing pass (HIP events): 100 whatever --steps is — the first launches
+  # after the queue has drained run slower (the driver's 20-step window averaged 17.9 us for a kernel
+  # that takes 15.5-16 us in steady state), so the pass also warms up before it arms the events
+  reps = 100
+  PROF_WARM = 8
+  gchunk = 10                               # steps per captured graph
+  Wg = -(-W // gchunk) * gchunk             # the graph mode's warm-up: W rounded up to whole chunks
+  # a short --steps window (the driver's 20 steps are 0.7 ms of GPU work) is reported next to a
+  # 200-step window of the same mode: `reference_window` in the JSON line
+  REFW = 200 if (K < 200 and not sharded and args.full) else 0
+  if sharded:
+    n_batches = K + W + 24
+  elif args.full:
+    n_batches = ((W + K) + (Wg + K) + 2 * reps + 14 + PROF_WARM + REFW +
+                 (0 if args.no_extra_windows else (W + K + 1) + REFW + 2 * (Wg + K + 8)))
+  else:   # warm-up, one eager step, the graph mode's rounded warm-up and the timed steps, + look-ahead
+    n_batches = W + min(K, 200) + 1 + Wg + K + 3
+  P = ring_size(n_batches, K, args.full, RING)
+
   def make_table(res):
-    rows_cap = res + (K + W + 8) * B * (2 if sharded else 1) + (1 << 16)
+    # room for a batch of new rows per step: K + W + 8 batches with a fresh batch for every step; when the
+    # batches come round, new ids come from the ring's P batches only
+    units = K + W + 8 if P == n_batches else min(K + W + 8, RING)
+    rows_cap = res + units * B * (2 if sharded else 1) + (1 << 16)
     slots = 4
     while slots * 0.5 < rows_cap:
       slots *= 2
@@ -799,24 +919,9 @@ def main():
   prefill_s = time.time() - t0
   st0 = mt.stats("emb")
 
-  # ---- inputs resident in HBM before the timed region ----
-  # Every launch mode trains FRESH batches (a replay of batches the table has already seen would
-  # find every id resident and skip the insert path).  The modes run back to back over one
-  # contiguous batch sequence: the last step of a mode deduplicates the first batch of the next
-  # mode ahead, exactly as it does inside a mode.
-  # launches of the per-kernel timing pass (HIP events): 100 whatever --steps is — the first launches
-  # after the queue has drained run slower (the driver's 20-step window averaged 17.9 us for a kernel
-  # that takes 15.5-16 us in steady state), so the pass also warms up before it arms the events
-  reps = 100
-  PROF_WARM = 8
-  gchunk = 10                               # steps per captured graph
-  Wg = -(-W // gchunk) * gchunk             # the graph mode's warm-up: W rounded up to whole chunks
-  # a short --steps window (the driver's 20 steps are 0.7 ms of GPU work) is reported next to a
-  # 200-step window of the same mode: `reference_window` in the JSON line
-  REFW = 200 if (K < 200 and not sharded) else 0
-  n_batches = ((W + K) + (Wg + K) + 2 * reps + 14 + PROF_WARM + REFW +
-               (0 if args.no_extra_windows else (W + K + 1) + REFW + 2 * (Wg + K + 8))) if not sharded else (K + W + 24)
-  ids_host = np.stack([S.id_batch(s * world + rank, B, V, "zipf") for s in range(n_batches)])
+  # ---- inputs resident in HBM before the timed region (their number P: above the table) ----
+  with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
+    ids_host = np.stack(list(ex.map(lambda s: S.id_batch(s * world + rank, B, V, "zipf"), range(P))))
   ids_all = torch.from_numpy(ids_host).to(dev)
   NG = max(1, args.grad_pool)
   grad_pool = [torch.from_numpy(S.grad_batch(s, B, D)).to(dev) for s in range(NG)]
@@ -831,6 +936,8 @@ def main():
 
   results = {}
   steps_of = {}
+  outputs = {}         # --dump-outputs: what each timed window's last step returned, by window
+  window_of = {}       # steps [lo, hi) of each timed window
   extra_windows = {}   # ms per step of the windows that are reported beside the line's own (eager_cpp, exact_order)
   stages, shard_info, shard_roofline, uniq_avg = {}, None, None, None
   graph_err = None
@@ -850,16 +957,24 @@ def main():
     def run_eager(lo, hi, st=None):
       st = st or step
       for s in range(lo, hi):
-        st.forward(ids_all[s], next_ids=ids_all[s + 1], ahead_ids=ids_all[s + 2] if two_ahead else None)
-        st.backward(grad_pool[s % NG], S.update_time(s))
-        applied.append((s, s % NG, S.update_time(s)))
+        b = s % P
+        st.forward(ids_all[b], next_ids=ids_all[(s + 1) % P],
+                   ahead_ids=ids_all[(s + 2) % P] if two_ahead else None)
+        st.backward(grad_pool[b % NG], S.update_time(b))
+        applied.append((b, b % NG, S.update_time(b)))
 
     def run_c_loop(lo, hi):
       # the same steps enqueued by a plain C loop over mhte_table_step_forward / _backward
-      # (csrc/eager_loop.c): no interpreter and no hipGraph between the calls
-      step.c_loop(ids_all, lo, hi, grad_pool, S.update_time(0))
-      for s in range(lo, hi):
-        applied.append((s, s % NG, S.update_time(s)))
+      # (csrc/eager_loop.c): no interpreter and no hipGraph between the calls.  The loop reads batch
+      # s + 1 ahead of step s: a stretch ends one step short of the ring's end, and that step (whose
+      # next batch is the ring's first) is enqueued from here
+      for b, n in ring_stretches(lo, hi, P):
+        if n is None:
+          run_eager(b, b + 1)
+          continue
+        step.c_loop(ids_all, b, b + n, grad_pool, S.update_time(0))
+        for b_ in range(b, b + n):
+          applied.append((b_, b_ % NG, S.update_time(b_)))
 
     def timed(name, c, w, k):
       import gc
@@ -873,16 +988,50 @@ def main():
       results[name] = time.perf_counter() - t
       gc.enable()
       steps_of[name] = k
+      window_of[name] = (c + w, c + w + k)
+      if args.dump_outputs:
+        outputs[name] = take_outputs({"embeddings": step.emb})
       return c + w + k
 
-    cur = timed("eager", 0, W, K)          # two launches per step
+    def capture(st, c0, n):
+      """hipGraphs of gc steps each for the steps [c0, c0 + n).  Past the ring's length one turn of it is
+      captured: graph i serves steps c0 + i * gc + j * P, which train the same batches (replay())."""
+      if n > P:
+        assert P % 60 == 0, "a ring of %d batches does not come back to its captured state" % P
+        n = P
+      gs = []
+      for a in range(c0, c0 + n, gc):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+          run_eager(a, a + gc, st)
+        gs.append(g)
+      return gs
+
+    def replay(gs, lo, hi):
+      """chunks [lo, hi) of the steps captured by capture(): a chunk past the ring replays its turn's graph
+      (the parity log then no longer lists every update)"""
+      nonlocal applied_ok
+      if hi > len(gs):
+        applied_ok = False
+      for i in range(lo, hi):
+        gs[i % len(gs)].replay()
+
+    gc = gchunk
+    want_graph = args.launch in ("auto", "graph") and K % gc == 0
+    if args.full or not want_graph:
+      cur = timed("eager", 0, W, K)          # two launches per step
+    else:
+      # the line's launch mode alone.  Warm-up: the W steps, then (untimed) the eager window that --full times
+      # ahead of the graph mode, at most 200 steps — a short graph window measured straight after a few steps
+      # read 33.9 us per step against 30.3 behind that window
+      cur = W + min(K, 200)
+      run_eager(0, cur)
 
     # ---- hipGraph replay: the launch-bound loop captured in chunks of `gc` pipelined steps
     # (2 launches per step on one queue).  Each chunk graph reads its batches straight from the
     # resident id array, so nothing is copied or skipped inside the timed region.
     # The warm-up is rounded UP to whole chunks (extra untimed steps); exactly K steps are timed.
-    gc = gchunk
-    if args.launch in ("auto", "graph") and K % gc == 0:
+    if want_graph:
       graphs = []
       try:
         # one eager step first: leaves batch cur+1 deduplicated ahead and a displacement pass
@@ -894,27 +1043,23 @@ def main():
         # (the reference window below is replayed too: enqueued step by step from the interpreter a
         # window is HOST-bound on a slow host — 41.9 us/step on one box against 30.4 replayed)
         n_ref = (REFW // gc) * gc
-        for c0 in range(G0, G0 + Wg + K + n_ref, gc):
-          g = torch.cuda.CUDAGraph()
-          with torch.cuda.graph(g):
-            run_eager(c0, c0 + gc)
-          graphs.append(g)
+        graphs = capture(step, G0, Wg + K + n_ref)
         cur = G0 + Wg + K + n_ref
         torch.cuda.synchronize()
         # capture executed nothing: replay from batch G0
-        for g in graphs[:Wg // gc]:
-          g.replay()
+        replay(graphs, 0, Wg // gc)
         barrier()
         t = time.perf_counter()
-        for g in graphs[Wg // gc:(Wg + K) // gc]:
-          g.replay()
+        replay(graphs, Wg // gc, (Wg + K) // gc)
         barrier()
         results["graph"] = time.perf_counter() - t
         steps_of["graph"] = K
+        window_of["graph"] = (G0 + Wg, G0 + Wg + K)
+        if args.dump_outputs:
+          outputs["graph"] = take_outputs({"embeddings": step.emb})
         if n_ref:
           t = time.perf_counter()
-          for g in graphs[(Wg + K) // gc:]:
-            g.replay()
+          replay(graphs, (Wg + K) // gc, (Wg + K + n_ref) // gc)
           barrier()
           results["graph_ref_window"] = time.perf_counter() - t
           steps_of["graph_ref_window"] = n_ref
@@ -927,6 +1072,8 @@ def main():
         # start the following passes from a fresh pipeline
         step = SparseStep(mt, "emb", B, exact_order=args.exact_order)
         cur += gc * (len(graphs) + 1)
+        if "eager" not in results:   # (the graph mode was to be the only one: the line's window enqueued eagerly)
+          cur = timed("eager", cur, W, K)
     if REFW and "graph_ref_window" not in results:   # (no graph mode: the long window enqueued step by step)
       cur = timed("eager_ref_window", cur, 0, REFW)
     # ---- two more windows of K steps, reported under timing_ms_per_step, never the line's `value`:
@@ -968,20 +1115,13 @@ def main():
           run_eager(cur, cur + 4, step_x)   # (every workspace of the new pipeline allocates outside the capture)
           cur += 4
           step_x.quiesce()
-          gx = []
-          for c0 in range(cur, cur + Wg + K, gchunk):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-              run_eager(c0, c0 + gchunk, step_x)
-            gx.append(g)
+          gx = capture(step_x, cur, Wg + K)
           cur += Wg + K
           torch.cuda.synchronize()
-          for g in gx[:Wg // gchunk]:
-            g.replay()
+          replay(gx, 0, Wg // gchunk)
           barrier()
           t = time.perf_counter()
-          for g in gx[Wg // gchunk:]:
-            g.replay()
+          replay(gx, Wg // gchunk, (Wg + K) // gchunk)
           barrier()
           extra_windows["exact_order"] = (time.perf_counter() - t) / K * 1e3
           del gx
@@ -1005,7 +1145,7 @@ def main():
     from tests.torch_sharded_step import HipBackend, ShardedEmbedding   # (test harness: last-resort fallback)
     from monolith_amd.multi_hash_table_ops import Ragged
     splits1 = np.array([0, B], dtype=np.int64)
-    rag = [Ragged(ids_all[s], splits1) for s in range(n_batches)]
+    rag = [Ragged(ids_all[s], splits1) for s in range(P)]
     emb_out = torch.empty(B * D, dtype=torch.float32, device=dev)
     impl = os.environ.get("MHTE_BENCH_SHARDED_IMPL", "")   # "torch": round 1's torch.distributed form
     if args.transport == "torch":
@@ -1112,12 +1252,13 @@ def main():
     def run_sharded(lo, hi):
       for s in range(lo, hi):
         t_a = time.perf_counter() if trace_host else 0.0
-        se.forward(rag[s], rag[s + 1], out=emb_out)
+        b = s % P
+        se.forward(rag[b], rag[(s + 1) % P], out=emb_out)
         t_b = time.perf_counter() if trace_host else 0.0
-        se.backward(grad_pool[s % NG].view(-1), S.update_time(s))
+        se.backward(grad_pool[b % NG].view(-1), S.update_time(b))
         if trace_host:
           host_us.append((s, (t_b - t_a) * 1e6, (time.perf_counter() - t_b) * 1e6))
-        applied.append((s, s % NG, S.update_time(s)))
+        applied.append((b, b % NG, S.update_time(b)))
 
     import gc
     run_sharded(0, W)
@@ -1131,9 +1272,12 @@ def main():
     barrier()
     results["eager"] = time.perf_counter() - t
     elapsed_local = results["eager"]
+    if args.dump_outputs:
+      outputs["eager"] = take_outputs({"embeddings": emb_out.view(B, D)})
     if gc_was:
       gc.enable()
     steps_of["eager"] = K
+    window_of["eager"] = (W, W + K)
     se.check()
     shard_info = se.info()
     if trace_host:
@@ -1143,7 +1287,7 @@ def main():
     if not args.no_stage_timing:   # kernel-exact time of every tagged launch of a step (every rank
                                    # runs the same extra steps: they are collective; rank 0 reports its own)
       acc = {}
-      nprof = min(20, n_batches - (W + K) - 1)
+      nprof = 20
       for s in range(W + K, W + K + nprof):
         _lib.profile_arm(64)
         run_sharded(s, s + 1)
@@ -1153,7 +1297,7 @@ def main():
           a[0] += 1
           a[1] += us
       if nprof > 0:
-        uniq_avg = float(np.mean([np.unique(ids_host[s]).size for s in range(W + K, W + K + nprof)]))
+        uniq_avg = float(np.mean([np.unique(ids_host[s % P]).size for s in range(W + K, W + K + nprof)]))
         salg = sharded_algorithmic_bytes(B, uniq_avg, D, S_state)
         stages = {"note": "kernel-exact HIP-event time of the tagged launches of the sharded step "
                           "(+ 1 untagged displacement launch per peer)"}
@@ -1225,15 +1369,16 @@ def main():
     us = []
     step.quiesce()
     for s in range(P0 + reps + 5, P0 + 2 * reps + 5):
-      ids = ids_all[s]
+      b = s % P
+      ids = ids_all[b]
       _lib.profile_arm(8)
       step._unique(ids)  # pylint: disable=protected-access
       mt.table_lookup_n(step.idx, ids, None, step.emb, n_max=B)
-      mt.table_sum_optimize_n(step.idx, step.ws, step.u, grad_pool[s % NG], step.grad_u, step.lrs,
-                              S.update_time(s), 0, exact_order=args.exact_order, n_max=B,
+      mt.table_sum_optimize_n(step.idx, step.ws, step.u, grad_pool[b % NG], step.grad_u, step.lrs,
+                              S.update_time(b), 0, exact_order=args.exact_order, n_max=B,
                               defer_slowpath=True)
       mt.table_finish_pending(step.idx)
-      applied.append((s, s % NG, S.update_time(s)))
+      applied.append((b, b % NG, S.update_time(b)))
       collect()
       us.append(step.n_unique())
     uniq_avg = float(np.mean(us))
@@ -1275,11 +1420,12 @@ def main():
   parity = None
   if rank == 0 and not args.no_parity_check:
     if not applied_ok:
-      parity = {"skipped": "update log invalid after a failed graph capture"}
+      parity = {"skipped": "update log incomplete: a failed graph capture, or graphs replayed more than once "
+                           "(more steps than distinct batches)"}
     else:
       try:
         last = applied[-1][0]
-        probe = np.unique(np.concatenate([ids_host[last], ids_host[W + K // 2]]))
+        probe = np.unique(np.concatenate([ids_host[last], ids_host[(W + K // 2) % P]]))
         lr = 0.001 if args.opt == "adagrad" else 0.01
         t0p = time.time()
         gcache = {}
@@ -1367,7 +1513,7 @@ def main():
   exchange_info = None
   if sharded and world > 1:
     nb = min(K, 16)
-    remote = float(np.mean([int((np.unique(ids_host[W + s]) % world != rank).sum()) for s in range(nb)]))
+    remote = float(np.mean([int((np.unique(ids_host[(W + s) % P]) % world != rank).sum()) for s in range(nb)]))
     egress = remote * (8 + 4 * D)          # ids + gradient sums leave
     ingress = remote * (4 * D)             # rows come back (+ the peers' ids and gradients: symmetric)
     per_step_s = elapsed / K
@@ -1381,20 +1527,18 @@ def main():
         "floor_us_at_xgmi_peak": round(max(egress, ingress + remote * 8) / (XGMI_PEAK * 1e9) * 1e6, 2),
         "note": "rank 0's bytes; the step's three exchanges are latency-bound at this size (SURVEY 8e)"}
   if rank == 0:
-    # A short window (the driver's 20 steps are 0.6 ms of GPU work: two hipGraph replays) is fragile:
-    # when the 200-step reference window of the same step disagrees with it by more than 3 %, the
-    # SLOWER of the two is what the line reports (both stay in timing_ms_per_step / reference_window).
-    per_step = elapsed / K
+    # The line is the --steps window's: a short window (the driver's 20 steps are 0.6 ms of GPU work: two
+    # hipGraph replays) is fragile, and --full reports the 200-step window of the same step beside it
+    # (reference_window).
     value_window = "%d steps, %s" % (K, launch)
+    repeated = repeated_steps(*window_of[launch], P) if launch in window_of else 0
+    if repeated:
+      value_window += ("; %d of them train batches an earlier step trained (a ring of %d distinct batches): "
+                       "their ids are all resident, nothing is inserted" % (repeated, P))
     ref_key = next((k for k in REF_KEYS if k in results), None)
-    if ref_key:
-      ref_ps = results[ref_key] / steps_of[ref_key]
-      if ref_ps > per_step * 1.03:
-        per_step = ref_ps
-        value_window = "%d-step reference window, %s (the %d-step %s window read %.2f us/step)" % (
-            steps_of[ref_key], ref_key.split("_")[0], K, launch, elapsed / K * 1e6)
-    elapsed = per_step * K
     value = 2.0 * B * K * world / elapsed
+    if args.dump_outputs:
+      write_outputs(args.dump_outputs, outputs[launch])
     out = {
         "metric": "embedding lookups+updates/sec at 1B ids x dim64, Zipf(1.2) batch=65536",
         "value": round(value, 1),
@@ -1420,6 +1564,9 @@ def main():
             "row_bytes": 4 * (D + S_state), "hashpower": int(st1.hashpower),
             "table_bytes_per_gpu": int(st1.bytes_buckets + st1.bytes_rows),
             "unique_ids_per_batch": uniq_avg, "launch": launch,
+            "distinct_batches": P,
+            "distinct_batches_note": "step s trains batch s mod %d of the seeded stream" % P,
+            "timed_steps_on_repeated_batches": repeated,
             "launch_note": ("hipGraph replay, %d steps per graph; %d untimed warm-up steps replayed "
                             "(--warmup rounded up to whole graphs), exactly %d steps timed" %
                             (gchunk, Wg, K)) if launch == "graph" else None,

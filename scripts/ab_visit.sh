@@ -6,7 +6,7 @@ OUT=gpurun_out/${1:-ab}; mkdir -p $OUT
 run() { # name env...
   local name=$1; shift
   for i in 1 2; do
-    env "$@" timeout 300 python bench.py --no-cpu-baseline --steps 200 --warmup 20 > $OUT/$name.$i.json 2> $OUT/$name.$i.err
+    env "$@" timeout 300 python bench.py --full --no-cpu-baseline --steps 200 --warmup 20 > $OUT/$name.$i.json 2> $OUT/$name.$i.err
     python - <<PY
 import json
 try:
