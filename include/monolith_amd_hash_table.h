@@ -42,7 +42,7 @@ enum {
 
 const char* mhte_last_error(void);
 /* ABI version of this header; mhte_abi_version() must return the same value. */
-#define MHTE_ABI_VERSION 17
+#define MHTE_ABI_VERSION 18
 int32_t mhte_abi_version(void);
 
 /* ---- configuration (flat C form of RT/hash_table/embedding_hash_table.proto) --------------- */
@@ -321,6 +321,43 @@ mhte_status mhte_fused_gather_embeddings_by_input_gradient(float* fused_grad, in
 mhte_status mhte_reduce_rows(const int64_t* indices, const float* values, int64_t n, int32_t dim,
                              int64_t batch, int32_t mode, int32_t indices_sorted, float* out,
                              void* stream);
+
+/* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
+ * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
+ * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op
+ * MonolithFusedReduceSumAndSplit (+Gradient) (RT/ops/reduce_op.cc:231-321, NT/distribution_ops.py:802-835)
+ * for one feature: the ragged sum of every feature's embedding rows per batch row, written straight into
+ * the column slices of the features — one launch for all features, one for the gradient.
+ *   row_splits         [dev i32] the features' row_splits (bs + 1 each) concatenated
+ *   row_split_splits   HOST [n_features + 1]: where each feature's begin (the op's attr);
+ *                      bs = row_split_splits[1] - row_split_splits[0] - 1 (reduce_op.cu.cc:417)
+ *   embeddings         HOST array of n_features device pointers, matrix i is [emb_rows[i], emb_dims[i]]
+ *   slice_dims         HOST, flat, in feature order (the op's attr): the widths the features' columns
+ *                      are cut into; a feature's slices add up to its dim
+ *   outputs            HOST array of n_slices device pointers, slice s is [bs, slice_dims[s]]
+ * out[b, c] = +0 + emb[rs[b], c] + emb[rs[b] + 1, c] + ... added strictly in row order (the reference
+ * kernel's `sum = T(0); sum += ...`, :308-316, and the CPU op's accumulation into a zeroed output,
+ * reduce_op.cc:253-270): the reference's bits, a row of -0.0 alone gives +0.0, an empty row +0.0; a batch
+ * row of any length is one sequential chain.  Ranges are clamped to [0, emb_rows[i]]: a malformed
+ * row_splits reads no row outside its matrix.  The gradient is a copy: embeddings_grad[i][r, :] = the
+ * feature's slice gradients at the batch row whose range holds r, side by side (:478-499); rows before
+ * rs[0] or from rs[bs] on are 0.  No float atomics; nothing is allocated but, beyond 32 lane-column
+ * units or 96 slices, the tables of the call (uploaded per call; any number of features and slices).
+ * 16-byte accesses where a feature's dim, its slices' starts and widths are multiples of 4 floats and
+ * its pointers 16-byte aligned, else 4-byte ones (same bits).
+ * InvalidArgument, checked on the host before any device call: a null argument, n_features <= 0, a
+ * non-positive dim, a feature whose number of row splits differs from bs + 1, sum(slice_dims) !=
+ * sum(emb_dims), a slice that straddles two features (the reference checks none of the last three). */
+mhte_status mhte_fused_reduce_and_split(const int32_t* row_splits, const int32_t* row_split_splits,
+                                        const float* const* embeddings, const int64_t* emb_rows,
+                                        const int32_t* emb_dims, int32_t n_features,
+                                        const int32_t* slice_dims, int32_t n_slices, float* const* outputs,
+                                        void* stream);
+mhte_status mhte_fused_reduce_and_split_grad(const int32_t* row_splits, const int32_t* row_split_splits,
+                                             const int64_t* emb_rows, const int32_t* emb_dims,
+                                             int32_t n_features, const int32_t* slice_dims, int32_t n_slices,
+                                             const float* const* slice_grads, float* const* embeddings_grad,
+                                             void* stream);
 
 /* MonolithEmbeddingToLayout / MonolithEmbeddingToLayoutGrad (RT/ops/fused_embedding_to_layout.cc
  * :1037-1066; CUDA kernels RT/ops/fused_embedding_to_layout.cu.cc:96-199,337-...; GatherEmb /

@@ -35,6 +35,7 @@
 #include "mhte_proto_config.h"
 #include <map>
 #include "mhte_pool_kernels.h"
+#include "mhte_pool_split_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
@@ -2392,6 +2393,188 @@ mhte_status mhte_reduce_rows(const int64_t* indices, const float* values, int64_
       if (cnt) HIP_OK(hipFreeAsync(cnt, st));
     }
     HIP_OK(hipGetLastError());
+  });
+}
+
+// ---- fused ragged reduce-and-split pooling (csrc/mhte_pool_split_kernels.h) ------------------------
+}  // extern "C"
+namespace mhte {
+// Checks the plan on the host (every failure InvalidArgument, before any HIP call), then launches the forward
+// (ptrs: embeddings read, slice_ptrs: outputs written) or the gradient (ptrs: embedding gradients written,
+// slice_ptrs: slice gradients read).
+static void reduce_split_launch(bool forward, const int32_t* row_splits, const int32_t* row_split_splits,
+                                float* const* ptrs, const int64_t* emb_rows, const int32_t* emb_dims,
+                                int32_t n_features, const int32_t* slice_dims, int32_t n_slices,
+                                float* const* slice_ptrs, hipStream_t st) {
+  const std::string op = forward ? "fused_reduce_and_split: " : "fused_reduce_and_split_grad: ";
+  auto bad = [&](const std::string& m) { throw Error(MHTE_INVALID_ARGUMENT, op + m); };
+  if (n_features <= 0) bad("n_features must be > 0, got " + std::to_string(n_features));
+  if (n_slices <= 0) bad("n_slices must be > 0, got " + std::to_string(n_slices));
+  if (!row_splits) bad("null argument: row_splits");
+  if (!row_split_splits) bad("null argument: row_split_splits");
+  if (!ptrs) bad(forward ? "null argument: embeddings" : "null argument: embeddings_grad");
+  if (!emb_rows) bad("null argument: emb_rows");
+  if (!emb_dims) bad("null argument: emb_dims");
+  if (!slice_dims) bad("null argument: slice_dims");
+  if (!slice_ptrs) bad(forward ? "null argument: outputs" : "null argument: slice_grads");
+  int64_t emb_cols = 0, slice_cols = 0;
+  for (int32_t i = 0; i < n_features; ++i) {
+    if (emb_dims[i] <= 0)
+      bad("embedding " + std::to_string(i) + " has the non-positive dim " + std::to_string(emb_dims[i]));
+    if (emb_rows[i] < 0)
+      bad("embedding " + std::to_string(i) + " has a negative row count " + std::to_string(emb_rows[i]));
+    emb_cols += emb_dims[i];
+  }
+  for (int32_t k = 0; k < n_slices; ++k) {
+    if (slice_dims[k] <= 0)
+      bad("slice " + std::to_string(k) + " has the non-positive dim " + std::to_string(slice_dims[k]));
+    slice_cols += slice_dims[k];
+  }
+  const int64_t bs64 = int64_t(row_split_splits[1]) - row_split_splits[0] - 1;   // reduce_op.cu.cc:417
+  if (bs64 < 0) bad("feature 0 has no row splits (a feature has batch size + 1 of them)");
+  for (int32_t i = 0; i < n_features; ++i) {
+    const int64_t cnt = int64_t(row_split_splits[i + 1]) - row_split_splits[i];
+    if (cnt != bs64 + 1)
+      bad("feature " + std::to_string(i) + " has " + std::to_string(cnt) + " row splits, feature 0 has " +
+          std::to_string(bs64 + 1) + " (batch size + 1)");
+  }
+  if (slice_cols != emb_cols)
+    bad("sum(slice_dims) = " + std::to_string(slice_cols) + " differs from sum(emb_dims) = " +
+        std::to_string(emb_cols));
+  const int32_t bs = int32_t(bs64);
+  std::vector<SplitSlice> slices(static_cast<size_t>(n_slices));
+  std::vector<int32_t> first_slice(size_t(n_features) + 1, 0);
+  {
+    int32_t k = 0;
+    for (int32_t i = 0; i < n_features; ++i) {
+      first_slice[size_t(i)] = k;
+      int32_t col = 0;
+      while (col < emb_dims[i]) {   // (k < n_slices: the sums are equal)
+        if (col + int64_t(slice_dims[k]) > emb_dims[i])
+          bad("slice " + std::to_string(k) + " (columns " + std::to_string(col) + " to " +
+              std::to_string(col + int64_t(slice_dims[k])) + " of feature " + std::to_string(i) +
+              ", which has " + std::to_string(emb_dims[i]) + ") straddles features " + std::to_string(i) +
+              " and " + std::to_string(i + 1));
+        slices[size_t(k)].out = slice_ptrs[k];
+        slices[size_t(k)].start = col;
+        slices[size_t(k)].dim = slice_dims[k];
+        col += slice_dims[k];
+        ++k;
+      }
+    }
+    first_slice[size_t(n_features)] = k;
+  }
+  for (int32_t i = 0; i < n_features; ++i)
+    if (!ptrs[i] && emb_rows[i] > 0)
+      bad(std::string("null argument: ") + (forward ? "embeddings[" : "embeddings_grad[") + std::to_string(i) + "]");
+  for (int32_t k = 0; k < n_slices; ++k)
+    if (!slice_ptrs[k] && bs > 0)
+      bad(std::string("null argument: ") + (forward ? "outputs[" : "slice_grads[") + std::to_string(k) + "]");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    throw Error(MHTE_UNAVAILABLE, "no HIP device: the MI355X engine has no CPU fallback");
+  }
+  if (forward && bs == 0) return;
+  // units: a feature's lane columns (float4s where its shape and pointers allow, else floats) in runs of 64
+  std::vector<SplitUnit> units;
+  int64_t need = 1;
+  for (int32_t i = 0; i < n_features; ++i) {
+    if (!forward && emb_rows[i] == 0) continue;
+    bool vec = emb_dims[i] % 4 == 0 && aligned16(ptrs[i]);
+    for (int32_t k = first_slice[size_t(i)]; vec && k < first_slice[size_t(i) + 1]; ++k)
+      vec = ((slices[size_t(k)].start | slices[size_t(k)].dim) & 3) == 0 && aligned16(slices[size_t(k)].out);
+    const int32_t per = vec ? 4 : 1, cols = emb_dims[i] / per;
+    for (int32_t c0 = 0; c0 < cols; c0 += kSplitUnitCols) {
+      SplitUnit u{};
+      u.emb = ptrs[i];
+      u.n_rows = emb_rows[i];
+      u.rs_off = row_split_splits[i];
+      u.dim = emb_dims[i];
+      u.col0 = c0 * per;
+      const int32_t nc = std::min(kSplitUnitCols, cols - c0);
+      u.width = nc * per;
+      u.slice0 = first_slice[size_t(i)];
+      u.n_slices = first_slice[size_t(i) + 1] - first_slice[size_t(i)];
+      u.vec = vec ? 1 : 0;
+      while ((1 << u.log2g) < nc) ++u.log2g;
+      need = std::max(need, (int64_t(bs) + (256 >> u.log2g) - 1) / (256 >> u.log2g));
+      units.push_back(u);
+    }
+  }
+  if (units.empty()) return;
+  // (row blocks per unit: enough to fill the chip several times over, the rest of the rows by grid stride)
+  const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(64, 32768 / int64_t(units.size())));
+  const uint32_t gx = uint32_t(std::min(need, cap));
+  SplitArgs A{};
+  A.row_splits = row_splits;
+  A.bs = bs;
+  const bool ext = units.size() > size_t(kSplitInlineUnits) || slices.size() > size_t(kSplitInlineSlices);
+  struct Tmp {   // (freed in stream order behind the kernels that read it)
+    char* d = nullptr;
+    hipStream_t st;
+    ~Tmp() {
+      if (d && hipFreeAsync(d, st) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(d);
+      }
+    }
+  } tmp;
+  tmp.st = st;
+  if (ext) {
+    const size_t o_slice = units.size() * sizeof(SplitUnit), total = o_slice + slices.size() * sizeof(SplitSlice);
+    std::vector<char> h(total);
+    memcpy(h.data(), units.data(), o_slice);
+    memcpy(h.data() + o_slice, slices.data(), total - o_slice);
+    void* d = nullptr;
+    if (hipMallocAsync(&d, total, st) != hipSuccess) {
+      (void)hipGetLastError();
+      HIP_OK(hipMalloc(&d, total));
+    }
+    tmp.d = static_cast<char*>(d);
+    PinnedStage::of(current_device()).upload(tmp.d, h.data(), total, st);   // (no wait for the stream)
+    A.x_units = reinterpret_cast<const SplitUnit*>(tmp.d);
+    A.x_slices = reinterpret_cast<const SplitSlice*>(tmp.d + o_slice);
+  } else {
+    std::copy(units.begin(), units.end(), A.units);
+    std::copy(slices.begin(), slices.end(), A.slices);
+  }
+  for (size_t base = 0; base < units.size(); base += 65535) {   // (grid.y holds 65 535 units)
+    A.unit_base = int32_t(base);
+    const dim3 grid(gx, uint32_t(std::min<size_t>(65535, units.size() - base)));
+    if (ext) {
+      if (forward) reduce_split_kernel<true, true><<<grid, 256, 0, st>>>(A);
+      else reduce_split_kernel<true, false><<<grid, 256, 0, st>>>(A);
+    } else {
+      if (forward) reduce_split_kernel<false, true><<<grid, 256, 0, st>>>(A);
+      else reduce_split_kernel<false, false><<<grid, 256, 0, st>>>(A);
+    }
+    HIP_OK(hipGetLastError());
+  }
+}
+}  // namespace mhte
+extern "C" {
+
+mhte_status mhte_fused_reduce_and_split(const int32_t* row_splits, const int32_t* row_split_splits,
+                                        const float* const* embeddings, const int64_t* emb_rows,
+                                        const int32_t* emb_dims, int32_t n_features,
+                                        const int32_t* slice_dims, int32_t n_slices, float* const* outputs,
+                                        void* stream) {
+  return guard([&] {
+    reduce_split_launch(true, row_splits, row_split_splits, (float* const*)embeddings, emb_rows, emb_dims,
+                        n_features, slice_dims, n_slices, outputs, S(stream));
+  });
+}
+
+mhte_status mhte_fused_reduce_and_split_grad(const int32_t* row_splits, const int32_t* row_split_splits,
+                                             const int64_t* emb_rows, const int32_t* emb_dims,
+                                             int32_t n_features, const int32_t* slice_dims, int32_t n_slices,
+                                             const float* const* slice_grads, float* const* embeddings_grad,
+                                             void* stream) {
+  return guard([&] {
+    reduce_split_launch(false, row_splits, row_split_splits, embeddings_grad, emb_rows, emb_dims, n_features,
+                        slice_dims, n_slices, (float* const*)slice_grads, S(stream));
   });
 }
 

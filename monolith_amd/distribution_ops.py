@@ -318,6 +318,137 @@ def reduce_sqrtn(id_indices, id_values, id_length, indices_sorted: bool = True):
 
 
 # ---------------------------------------------------------------------------------------------
+# fused reduce-and-split pooling (reference distribution_ops.py:802-884; PoolingHelper of feature.py:501-541)
+# ---------------------------------------------------------------------------------------------
+def _split_plan(splits, rows, dims, slice_dims, dev):
+  """-> (fused row splits on the device, the ctypes arrays of the plan); ``slice_dims`` is flattened as the
+  reference flattens it (distribution_ops.py:852-862)."""
+  flat_slice_dims, row_split_splits = [], [0]
+  for s in slice_dims:
+    flat_slice_dims.extend(int(d) for d in s)
+  for sp in splits:
+    row_split_splits.append(row_split_splits[-1] + int(sp.shape[0]))
+  fused = [sp.to(device=dev, dtype=torch.int32).reshape(-1) for sp in splits]
+  fused_splits = (torch.cat(fused) if len(fused) != 1 else fused[0]).contiguous()
+  n = len(rows)
+  return (fused_splits, flat_slice_dims, (C.c_int32 * len(row_split_splits))(*row_split_splits),
+          (C.c_int64 * max(n, 1))(*rows), (C.c_int32 * max(n, 1))(*dims),
+          (C.c_int32 * max(len(flat_slice_dims), 1))(*flat_slice_dims))
+
+
+def _aligned_slices(batch: int, flat_slice_dims: List[int], dev) -> List[torch.Tensor]:
+  """[batch, d] tensors carved from ONE allocation, every start 16-byte aligned (the reference's
+  FusedAlignedOutputAllocator): the 16-byte path applies to each of them."""
+  starts, total = [], 0
+  for d in flat_slice_dims:
+    starts.append(total)
+    total += (batch * d + 3) // 4 * 4
+  buf = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+  return [buf[o:o + batch * d].view(batch, d) for o, d in zip(starts, flat_slice_dims)]
+
+
+def fused_reduce_and_split_gpu(splits: List[torch.Tensor], embeddings: List[torch.Tensor],
+                               slice_dims: List[List[int]]) -> List[torch.Tensor]:
+  """distribution_ops.fused_reduce_and_split_gpu (reference :838-871, MonolithFusedReduceAndSplitGPU).
+
+  Args:
+    splits: list of N 'row_splits' of fid ragged tensors (batch size + 1 entries each)
+    embeddings: list of N embeddings, the i-th [n_i, dim_i]
+    slice_dims: list of N slice_dims; sum(slice_dims[i]) = dim_i
+  Output:
+    reduced: M output tensors, the i-th of shape [bs, flat_slice_dims[i]], where
+    flat_slice_dims = concat(slice_dims) and M = len(flat_slice_dims): the sum of every feature's rows per
+    batch row, in row order from +0 (the reference's bits), cut into the feature's column slices.  One launch."""
+  if len(splits) != len(embeddings) or len(slice_dims) != len(embeddings):
+    raise _lib.InvalidArgumentError(
+        _lib.MHTE_INVALID_ARGUMENT, "fused_reduce_and_split_gpu: %d splits, %d embeddings, %d slice_dims" %
+        (len(splits), len(embeddings), len(slice_dims)))
+  dev = embeddings[0].device if embeddings else torch.device("cuda")
+  embs = [e.to(device=dev, dtype=torch.float32).contiguous() for e in embeddings]
+  assert all(e.dim() == 2 for e in embs)
+  fused_splits, flat, rss, rows, dims, sdims = _split_plan(
+      splits, [int(e.shape[0]) for e in embs], [int(e.shape[1]) for e in embs], slice_dims, dev)
+  batch = max(int(splits[0].shape[0]) - 1, 0) if splits else 0
+  outs = _aligned_slices(batch, flat, dev)
+  check(_lib.lib().mhte_fused_reduce_and_split(
+      vp(fused_splits), rss, _ptr_array(embs), rows, dims, C.c_int32(len(embs)), sdims,
+      C.c_int32(len(flat)), _ptr_array(outs), _stream()))
+  return outs
+
+
+def fused_reduce_and_split_gpu_grad(splits: List[torch.Tensor], embeddings: List[torch.Tensor],
+                                    slice_grads: List[torch.Tensor],
+                                    slice_dims: List[List[int]]) -> List[torch.Tensor]:
+  """The gradient of ``fused_reduce_and_split_gpu`` (reference :874-884, MonolithFusedReduceAndSplitGPUGrad):
+  for every embedding (only its shape is used) a gradient of the same shape — row r takes the feature's
+  slice gradients, side by side, at the batch row whose range holds r; a row outside every range is 0."""
+  if len(splits) != len(embeddings) or len(slice_dims) != len(embeddings):
+    raise _lib.InvalidArgumentError(
+        _lib.MHTE_INVALID_ARGUMENT, "fused_reduce_and_split_gpu_grad: %d splits, %d embeddings, %d slice_dims" %
+        (len(splits), len(embeddings), len(slice_dims)))
+  dev = slice_grads[0].device if slice_grads else torch.device("cuda")
+  fused_splits, flat, rss, rows, dims, sdims = _split_plan(
+      splits, [int(e.shape[0]) for e in embeddings], [int(e.shape[1]) for e in embeddings], slice_dims, dev)
+  batch = max(int(splits[0].shape[0]) - 1, 0) if splits else 0
+  if len(slice_grads) != len(flat) or any(tuple(g.shape) != (batch, d) for g, d in zip(slice_grads, flat)):
+    raise _lib.InvalidArgumentError(
+        _lib.MHTE_INVALID_ARGUMENT,
+        "fused_reduce_and_split_gpu_grad: slice_grads must be [bs = %d, d] for d in %s" % (batch, flat))
+  gs = [g.to(device=dev, dtype=torch.float32).contiguous() for g in slice_grads]
+  grads = [torch.empty((int(e.shape[0]), int(e.shape[1])), dtype=torch.float32, device=dev)
+           for e in embeddings]
+  check(_lib.lib().mhte_fused_reduce_and_split_grad(
+      vp(fused_splits), rss, rows, dims, C.c_int32(len(grads)), sdims, C.c_int32(len(flat)),
+      _ptr_array(gs), _ptr_array(grads), _stream()))
+  return grads
+
+
+def _row_splits_of_sorted(id_indices: torch.Tensor, batch: int) -> torch.Tensor:
+  idx = id_indices.reshape(-1).to(dtype=torch.int64).contiguous()
+  edges = torch.arange(batch + 1, dtype=torch.int64, device=idx.device)
+  return torch.searchsorted(idx, edges).to(torch.int32)
+
+
+def _unsorted_route(name):
+  raise NotImplementedError(
+      "%s: indices_sorted=False has no device path; reduce_sum(..., indices_sorted=False) followed by "
+      "torch.split is the route for row indices in any order" % name)
+
+
+def fused_reduce_sum_and_split(id_indices: torch.Tensor, id_values: torch.Tensor, id_length,
+                               split_dims: List[int], indices_sorted: bool = True) -> List[torch.Tensor]:
+  """distribution_ops.fused_reduce_sum_and_split (reference :802-826, MonolithFusedReduceSumAndSplit): very
+  similar to a sparse reduce_sum, combined with a fused split.
+
+  Args:
+    id_indices: 1-D tensor, the batch row of every row of id_values (ascending).
+    id_values: 2-D tensor, a list of actual values.
+    id_length: the batch size.
+    split_dims: dimensions of the split vectors; sum(split_dims) = id_values.shape[1].
+  Output:
+    reduced: M output tensors, the i-th of shape [bs, split_dims[i]]."""
+  if not indices_sorted:
+    _unsorted_route("fused_reduce_sum_and_split")
+  batch = id_length if isinstance(id_length, int) else int(torch.as_tensor(id_length).reshape(-1)[0])
+  assert id_values.is_cuda and id_values.dim() == 2 and id_indices.numel() == id_values.shape[0]
+  splits = _row_splits_of_sorted(id_indices.to(id_values.device), batch)
+  return fused_reduce_and_split_gpu([splits], [id_values], [list(split_dims)])
+
+
+def fused_reduce_sum_and_split_gradient(id_indices: torch.Tensor, grads: List[torch.Tensor],
+                                        split_dims: List[int], indices_sorted: bool = True) -> torch.Tensor:
+  """MonolithFusedReduceSumAndSplitGradient (reference :829-835): the gradient of id_values,
+  [len(id_indices), sum(split_dims)] — row i is the slices' gradients at batch row id_indices[i]."""
+  if not indices_sorted:
+    _unsorted_route("fused_reduce_sum_and_split_gradient")
+  dev = grads[0].device
+  batch = int(grads[0].shape[0])
+  splits = _row_splits_of_sorted(id_indices.to(dev), batch)
+  shape = torch.empty((int(id_indices.numel()), int(sum(split_dims))), device="meta")
+  return fused_reduce_and_split_gpu_grad([splits], [shape], list(grads), [list(split_dims)])[0]
+
+
+# ---------------------------------------------------------------------------------------------
 # fused_embedding_to_layout (reference distribution_ops.fused_embedding_to_layout and its gradient;
 # configuration messages of idl/matrix/proto/example.proto:176-221 as plain Python objects)
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Measurements for the rows next to the hot path, one JSON object per line + a markdown
 table: checkpoint save / restore, TTL eviction scan, admission filter inside the training step,
-post-exchange gather (+ gradient), ragged reductions, and the op-level update of every optimizer.
+post-exchange gather (+ gradient), ragged reductions, the fused reduce-and-split pooling against its
+composed form, and the op-level update of every optimizer.
 
 Every kernel here is HBM-streaming or random-row work, so each line carries algorithmic bytes,
 GB/s and the fraction of the 8 TB/s HBM peak; the checkpoint lines are host-codec bound (snappy +
@@ -252,6 +253,88 @@ def bench_reduce():
   emit("reduce_sum, unsorted indices (grouped in-order sums; MHTE_POOL_ATOMICS=1: float atomics)", t, alg + batch * dim * 4)
 
 
+def event_time(fn, reps=20):
+  """Mean seconds per call between two device events around ``reps`` calls."""
+  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  a.record()
+  for _ in range(reps):
+    fn()
+  b.record()
+  b.synchronize()
+  return a.elapsed_time(b) * 1e-3 / reps
+
+
+def bench_fused_reduce_split():
+  """fused_reduce_and_split_gpu and its gradient (one launch each) against the composed form on the ops
+  that were there before them: 26 x reduce_sum(sorted) + torch.split made contiguous, and 26 x index_select
+  + cat for the gradient.  26 features of dims 16/32/64 cycled, batch 65 536, skewed row lengths (half the
+  rows empty, mean about 2, a few rows of >= 1 000 ids).  Warm first, then fused and composed alternate
+  three times in this process, device events around 20 calls each."""
+  rng = np.random.default_rng(7)
+  bs, nfeat = 65536, 26
+  dims = [(16, 32, 64)[i % 3] for i in range(nfeat)]
+  slice_dims = [{16: [4, 12], 32: [8, 8, 16], 64: [16, 48]}[d] for d in dims]
+  splits, rowids, embs, n_rows = [], [], [], []
+  for i, d in enumerate(dims):
+    lens = rng.geometric(0.25, size=bs) * (rng.random(bs) < 0.5)
+    lens[rng.integers(0, bs, 3)] = rng.integers(1000, 3000, 3)
+    rs = np.concatenate([[0], np.cumsum(lens)])
+    n = int(rs[-1])
+    n_rows.append(n)
+    splits.append(torch.from_numpy(rs.astype(np.int32)).to(DEV))
+    rowids.append(torch.from_numpy(np.repeat(np.arange(bs), lens)).to(DEV))
+    embs.append(torch.randn((n, d), dtype=torch.float32, device=DEV))
+  flat = [d for s in slice_dims for d in s]
+  slice_grads = [torch.randn((bs, d), dtype=torch.float32, device=DEV) for d in flat]
+  first = np.concatenate([[0], np.cumsum([len(s) for s in slice_dims])])
+  emb_bytes = sum(n * d * 4 for n, d in zip(n_rows, dims))
+  out_bytes = bs * sum(dims) * 4
+  split_bytes = nfeat * (bs + 1) * 4
+  shape = dict(rows=int(sum(n_rows)), mean_len=round(sum(n_rows) / (nfeat * bs), 2),
+               longest_row=int(max(int(torch.diff(s).max()) for s in splits)))
+
+  def fused_fwd():
+    return D.fused_reduce_and_split_gpu(splits, embs, slice_dims)
+
+  def composed_fwd():
+    outs = []
+    for i in range(nfeat):
+      pooled = D.reduce_sum(rowids[i], embs[i], bs, indices_sorted=True)
+      outs.extend(p.contiguous() for p in torch.split(pooled, slice_dims[i], 1))
+    return outs
+
+  def fused_bwd():
+    return D.fused_reduce_and_split_gpu_grad(splits, embs, slice_grads, slice_dims)
+
+  def composed_bwd():
+    return [torch.index_select(torch.cat(slice_grads[first[i]:first[i + 1]], 1), 0, rowids[i])
+            for i in range(nfeat)]
+
+  for a, b in zip(fused_fwd(), composed_fwd()):
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+  for a, b in zip(fused_bwd(), composed_bwd()):
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+  for fn in (fused_fwd, composed_fwd, fused_bwd, composed_bwd):   # warm
+    for _ in range(5):
+      fn()
+  torch.cuda.synchronize()
+  rows = (("fused_reduce_and_split_gpu (26 features, dims 16/32/64, batch 65 536; 1 launch)", fused_fwd,
+           emb_bytes + split_bytes + out_bytes),
+          ("composed forward: 26 x reduce_sum(sorted) + torch.split made contiguous", composed_fwd,
+           emb_bytes + sum(n_rows) * 8 + 3 * out_bytes),
+          ("fused_reduce_and_split_gpu_grad (same shapes; 1 launch)", fused_bwd,
+           emb_bytes + split_bytes + out_bytes),
+          ("composed gradient: 26 x (cat of the slice gradients + index_select)", composed_bwd,
+           2 * emb_bytes + sum(n_rows) * 8 + 2 * out_bytes))
+  times = {name: [] for name, _, _ in rows}
+  for _ in range(3):
+    for name, fn, _ in rows:
+      times[name].append(event_time(fn, 20))
+  for name, fn, alg in rows:
+    t = sorted(times[name])
+    emit(name, t[1], alg, us_runs=[round(x * 1e6, 1) for x in times[name]], **shape)
+
+
 def bench_layout():
   """fused_embedding_to_layout, the GENERAL form: 8 pooled features (1-4 fids per batch row, Zipf row
   choice: hot rows are referenced from hundreds of batch rows), dim 32 + bias, CONCAT + ADDN."""
@@ -327,7 +410,7 @@ def main():
     gc.collect()
     gc.disable()   # (a generation-2 pass of the interpreter is ~40 ms: it would land in a 60-step window)
     {"optimizers": bench_optimizers, "step_optimizers": bench_step_optimizers, "gather": bench_gather,
-     "reduce": bench_reduce, "layout": bench_layout,
+     "reduce": bench_reduce, "layout": bench_layout, "fused_reduce_split": bench_fused_reduce_split,
      "evict": bench_evict, "filter": bench_filter_step, "checkpoint": bench_checkpoint}[w]()
   md = ["| Measurement | time | algorithmic bytes | GB/s | of 8 TB/s | notes |", "|---|---|---|---|---|---|"]
   for r in LINES:
