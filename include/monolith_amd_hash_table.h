@@ -42,7 +42,7 @@ enum {
 
 const char* mhte_last_error(void);
 /* ABI version of this header; mhte_abi_version() must return the same value. */
-#define MHTE_ABI_VERSION 18
+#define MHTE_ABI_VERSION 19
 int32_t mhte_abi_version(void);
 
 /* ---- configuration (flat C form of RT/hash_table/embedding_hash_table.proto) --------------- */
@@ -871,6 +871,10 @@ mhte_status mhte_dense_mlp_forward(mhte_dense_mlp* m, const float* x, int64_t ba
                                    void* stream);
 mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* dx,
                                     float learning_rate, void* stream);
+/* Read-only: GEMM launches of this handle since create, by role and tile shape (tests assert which
+ * instantiation a shape reached).  out[2 * role + tile]: role 0 forward, 1 gradient of a hidden
+ * layer, 2 gradient of the input (dx), 3 weight gradient; tile 0 = 128 x 128, 1 = 256 x 256. */
+mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]);
 
 /* ---- measurement aid (no reference counterpart) ---------------------------------------------
  * Kernel-exact timing of the hot kernels for bench.py's `roofline`: after mhte_profile_arm(n) the

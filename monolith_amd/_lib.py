@@ -26,7 +26,7 @@ MHTE_SUM_DUPLICATES = 2
 MHTE_EXACT_ORDER = 1       # flags of mhte_table_sum_optimize_n
 MHTE_DEFER_SLOWPATH = 2
 MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS = 1
-ABI_VERSION = 18           # MHTE_ABI_VERSION of include/monolith_amd_hash_table.h
+ABI_VERSION = 19           # MHTE_ABI_VERSION of include/monolith_amd_hash_table.h
 
 OPT_SGD, OPT_ADAGRAD, OPT_FTRL = 0, 1, 2
 OPT_MOMENTUM, OPT_ADADELTA, OPT_RMSPROP, OPT_RMSPROPV2, OPT_ADAM, OPT_AMSGRAD = 3, 4, 5, 6, 7, 8
@@ -216,6 +216,7 @@ EXPORTS = [
     "mhte_embedding_to_layout", "mhte_embedding_to_layout_grad",
     "mhte_dense_mlp_create", "mhte_dense_mlp_destroy", "mhte_dense_mlp_set_params",
     "mhte_dense_mlp_get_params", "mhte_dense_mlp_forward", "mhte_dense_mlp_backward",
+    "mhte_dense_mlp_launch_counts",
     "mhte_fused_reduce_and_split", "mhte_fused_reduce_and_split_grad",
 ]
 

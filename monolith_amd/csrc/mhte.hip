@@ -5187,6 +5187,13 @@ mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* d
     m->m.backward(dy, dx, learning_rate, S(stream));
   });
 }
+mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]) {
+  return guard([&] {
+    if (!m || !out) throw Error(MHTE_INVALID_ARGUMENT, "dense mlp: null argument");
+    for (int r = 0; r < 4; ++r)
+      for (int t = 0; t < 2; ++t) out[2 * r + t] = m->m.launches[r][t];
+  });
+}
 
 mhte_status mhte_trace_begin(void* dev_buf, int64_t cap_records) {
   return guard([&] {

@@ -31,6 +31,7 @@ struct DenseMlp {
   DevBuf<float> w_last, b_last, part_last;   // the row-dot layer: w [K], b [1]; per-block partial sums
   DevBuf<uint16_t> xb, xt;                   // the input as bf16 [B][w0] and transposed
   int64_t batch = 0;                         // of the last forward
+  int64_t launches[4][2] = {};               // GEMM launches by role (GemmEpilogue) and tile: [.][0] 128, [.][1] 256
 
   void create(const int32_t* w, int32_t n, int64_t mb, int dev) {
     if (n < 2) throw Error(MHTE_INVALID_ARGUMENT, "dense mlp: at least one hidden layer and the output");
@@ -110,16 +111,18 @@ struct DenseMlp {
 
   // 256 x 256 tiles (8 wavefronts) when the shape allows, else 128 x 128 (4)
   template <int EPI>
-  static void gemm(const GemmArgs& g, uint32_t nsplit, hipStream_t st) {
+  void gemm(const GemmArgs& g, uint32_t nsplit, hipStream_t st) {
     static const bool small_only = getenv("MHTE_GEMM_TILE128") != nullptr;   // (A/B runs)
     // (a small output — the weight gradients — is split along K: the larger tile pays only when it
     // still gives every CU a workgroup)
     if (g.M % 256 == 0 && g.N % 256 == 0 && !small_only &&
         uint64_t(g.M / 256) * (g.N / 256) * nsplit >= 256) {
       const dim3 grid(g.N / 256, g.M / 256, nsplit);
+      ++launches[EPI][1];
       LAUNCH_HOT(kTagGemm, (gemm_nt_bf16_kernel<EPI, 4, 2, 2, 4>), grid, 512, st, g);
     } else {
       const dim3 grid(g.N / 128, g.M / 128, nsplit);
+      ++launches[EPI][0];
       LAUNCH_HOT(kTagGemm, (gemm_nt_bf16_kernel<EPI, 2, 2, 2, 2>), grid, 256, st, g);
     }
     HIP_OK(hipGetLastError());

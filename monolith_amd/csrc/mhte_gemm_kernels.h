@@ -32,10 +32,12 @@ constexpr int kGemmLdsRow = kGemmBK + 8;   // bf16 elements per LDS row (144 byt
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {   // round to nearest even
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return uint16_t(u >> 16);
+// round to nearest even; a NaN stays one (quiet, sign kept).  The conversion instruction of gfx950
+// (v_cvt_pk_bf16_f32): the integer form u + 0x7fff + lsb carried a full-mantissa NaN (0x7fffffff,
+// 0xffffffff) through the exponent into the sign and left a zero, and a NaN test in front of it cost
+// the tower 3 % of its step
+__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
+  return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f));
 }
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(uint32_t(h) << 16); }
 // LDS traffic of ONE wavefront: its accesses complete in order, the wait makes them visible to itself
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M* WAVES_N == 4 ? 2 :
               float v = acc[i][jp * 2 + j2][q * 4 + r];
               if (EPI == kEpiFwd) {
                 v += bias;
-                if (g.relu) v = fmaxf(v, 0.f);
+                if (g.relu) v = v < 0.f ? 0.f : v;   // (fmaxf would turn a NaN into 0)
               }
               h[r] = f32_to_bf16(v);
               T[(ml + uint32_t(r)) * kTRow + nl] = h[r];

@@ -77,6 +77,15 @@ class DenseMlp:
                                                  self._stream()))
     return dx
 
+  GEMM_ROLES = ("forward", "dgrad", "dgrad_input", "wgrad")
+
+  def launch_counts(self):
+    """{role: (launches with the 128 x 128 tile, with the 256 x 256 tile)} of this handle's GEMMs since
+    it was created (mhte_dense_mlp_launch_counts): which instantiation a shape reached."""
+    out = (C.c_int64 * 8)()
+    _lib.check(self._lib.mhte_dense_mlp_launch_counts(self._h, out))
+    return {r: (int(out[2 * i]), int(out[2 * i + 1])) for i, r in enumerate(self.GEMM_ROLES)}
+
   def close(self):
     if getattr(self, "_h", None):
       torch.cuda.synchronize(self._device)

@@ -71,4 +71,10 @@ mhte_status mhte_dense_mlp_forward(mhte_dense_mlp* m, const float* x, int64_t ba
 mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* dx, float lr, void* st) {
   return guard([&] { m->m.backward(dy, dx, lr, S(st)); });
 }
+mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]) {
+  return guard([&] {
+    for (int r = 0; r < 4; ++r)
+      for (int t = 0; t < 2; ++t) out[2 * r + t] = m->m.launches[r][t];
+  });
+}
 }

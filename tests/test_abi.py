@@ -32,6 +32,17 @@ def test_library_builds_and_exports_header_symbols():
   assert L.mhte_abi_version() == _lib.ABI_VERSION
 
 
+def test_dense_mlp_launch_counts_on_the_whole_surface():
+  """ABI 19: the read-only GEMM launch counters are declared in the header, listed in _lib.EXPORTS,
+  exported by the library and reachable from the Python class."""
+  name = "mhte_dense_mlp_launch_counts"
+  assert name in _declared_symbols() and name in _lib.EXPORTS
+  assert hasattr(C.CDLL(_lib.build_library()), name)
+  assert re.search(r"#define\s+MHTE_ABI_VERSION\s+19\b", open(HEADER).read()) and _lib.ABI_VERSION == 19
+  from monolith_amd.dense_mlp import DenseMlp
+  assert callable(DenseMlp.launch_counts) and len(DenseMlp.GEMM_ROLES) == 4
+
+
 def test_library_contains_gfx950_code_object():
   so = _lib.build_library()
   out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-S", so], capture_output=True,
