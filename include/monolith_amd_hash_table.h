@@ -876,6 +876,49 @@ mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* d
  * layer, 2 gradient of the input (dx), 3 weight gradient; tile 0 = 128 x 128, 1 = 256 x 256. */
 mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]);
 
+/* ---- touched-key set (additive to ABI 19: new symbols only, nothing existing changes) ----------
+ * The set of keys (int64 fid, int32 tag) that an update path changed since the last steal: the
+ * HopscotchHashSet of RT/hopscotch/hopscotch_hash_set.cc:104-122,173-195 that the table bridge fills
+ * on every Optimize / BatchOptimize / Reinitialize (RT/ops/embedding_hash_table_tf_bridge.cc:247-251,
+ * 332-336,352-354) and the parameter-sync client drains (RT/ops/parameter_sync_tf_bridge.cc:70-90);
+ * also the stand-alone op of NT/touched_key_set_ops.py (tag 0).  It lives on the device: an insert
+ * allocates nothing and never synchronises with the host, so a step that records stays capturable.
+ * Rule, key by key in segment-major then position-minor order: a set holding more than `capacity`
+ * keys is dropped whole (dropped += size, clears += 1) before the key is added.  The reference's loss
+ * of a key whose hopscotch displacement fails is not mirrored: this is the mathematical set.
+ * Every int64 is a legal fid; tags are >= 0 (an attached set uses the table index).
+ * max_insert (0 = capacity + 1) bounds the positions of one device call and with them the memory:
+ * 16 bytes x the power of two >= 2 * (capacity + 1 + max_insert) slots; longer inputs are cut into
+ * several calls here.  Consecutive calls on different streams are ordered by an event. */
+typedef struct mhte_touched_key_set mhte_touched_key_set;
+mhte_status mhte_touched_key_set_create(int64_t capacity, int64_t max_insert, int32_t device,
+                                        mhte_touched_key_set** out);
+/* also detaches the set from the MultiHashTable it is attached to */
+void mhte_touched_key_set_destroy(mhte_touched_key_set* set);
+/* ids [dev, n_max]; n_dev [dev u32] or NULL (= n_max): the number of leading ids that count */
+mhte_status mhte_touched_key_set_insert(mhte_touched_key_set* set, const int64_t* ids, int64_t n_max,
+                                        const uint32_t* n_dev, int32_t tag, void* stream);
+/* out [host]: size, keys dropped by clears, clears, capacity.  Waits for the stream. */
+mhte_status mhte_touched_key_set_stats(mhte_touched_key_set* set, int64_t out[4], void* stream);
+/* GetAndClear: ids_out [dev, cap], tags_out [dev, cap] or NULL, *n [host] = keys written, in no
+ * particular order.  cap < size: MHTE_INVALID_ARGUMENT and the set is untouched; cap >= capacity + 1
+ * always suffices.  Waits for the stream.  Neither `dropped` nor `clears` changes. */
+mhte_status mhte_touched_key_set_steal(mhte_touched_key_set* set, int64_t* ids_out, int32_t* tags_out,
+                                       int64_t cap, int64_t* n, void* stream);
+/* Attaches the set (NULL detaches): from here on mhte_optimize, mhte_fused_optimize, mhte_reinitialize,
+ * mhte_table_optimize_n, mhte_table_sum_optimize_n, mhte_table_step_backward(_ahead) and
+ * mhte_multi_step_backward insert (id, table index) for the ids they update — the step entry points
+ * from the step's unique ids and device-side count, the multi-table step with ONE insert call over all
+ * tables.  Assign, AssignAdd and lookups never record.  With an admission filter attached as well, the
+ * op-level entry points record the ids the table holds after the update (ids_after_filter of the
+ * bridge; the one recording path that may allocate and synchronise: its probe buffer grows when a call
+ * brings more ids than any before it); the fused-step entry points refuse the combination with MHTE_INVALID_ARGUMENT (the single
+ * table step at the call, the multi step at its creation and here), as the id-sharded step's creation
+ * refuses a table with a set, and attaching here is refused while an id-sharded step of the table exists.
+ * One set serves one MultiHashTable on its own device; destroying either side detaches.  A MultiHashTable may
+ * be destroyed before or after the steps created on it. */
+mhte_status mhte_multi_table_set_touched_key_set(mhte_multi_table* t, mhte_touched_key_set* set);
+
 /* ---- measurement aid (no reference counterpart) ---------------------------------------------
  * Kernel-exact timing of the hot kernels for bench.py's `roofline`: after mhte_profile_arm(n) the
  * next n launches of the step kernels made by the calling thread go through

@@ -218,6 +218,8 @@ EXPORTS = [
     "mhte_dense_mlp_get_params", "mhte_dense_mlp_forward", "mhte_dense_mlp_backward",
     "mhte_dense_mlp_launch_counts",
     "mhte_fused_reduce_and_split", "mhte_fused_reduce_and_split_grad",
+    "mhte_touched_key_set_create", "mhte_touched_key_set_destroy", "mhte_touched_key_set_insert",
+    "mhte_touched_key_set_stats", "mhte_touched_key_set_steal", "mhte_multi_table_set_touched_key_set",
 ]
 
 _lib = None
@@ -266,6 +268,8 @@ def lib():
     L.mhte_hash_filter_destroy.argtypes = [C.c_void_p]
     L.mhte_multi_table_destroy.argtypes = [C.c_void_p]
     L.mhte_dedup_ws_destroy.argtypes = [C.c_void_p]
+    L.mhte_touched_key_set_destroy.restype = None
+    L.mhte_touched_key_set_destroy.argtypes = [C.c_void_p]
     for name in ("mhte_num_tables",):
       getattr(L, name).argtypes = [C.c_void_p]
     for name in ("mhte_table_name", "mhte_table_dim", "mhte_table_slice_size",

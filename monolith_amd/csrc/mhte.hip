@@ -1530,6 +1530,12 @@ struct mhte_multi_table {
   // device copies of the tables' views, read by the multi-table launches (mhte_mstep_host.h)
   mhte::DevBuf<mhte::TableView> d_views;
   std::vector<uint64_t> view_uploaded;
+  // the attached touched-key set (mhte_touched_host.h); read under a table's mutex, written under all
+  mhte_touched_key_set* touched = nullptr;
+  // live step objects, under g_touched_link_mu (a filter and a set together refuse a multi step, a set
+  // refuses an id-sharded step); destroying the table first unlinks them
+  std::vector<mhte_multi_step*> multi_steps;
+  std::vector<mhte_shard_step*> shard_steps;
 };
 struct mhte_dedup_ws {
   mhte::DedupWs ws;
@@ -1569,6 +1575,36 @@ struct mhte_hash_filter {
     if (state) (void)hipFree(state);
   }
 };
+
+// the read-only probe (mhte_table_contains; the touched-key set's record of a filtered table)
+namespace mhte {
+__global__ __launch_bounds__(256) void contains_kernel(TableView tv, const int64_t* __restrict__ ids,
+                                                       const uint32_t* __restrict__ n_dev, int64_t n,
+                                                       int32_t* __restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (n_dev && i >= int64_t(*n_dev)) {   // (behind the device-side count: not held)
+    out[i] = 0;
+    return;
+  }
+  const int64_t id = ids[i];
+  if (id == kEmptyKey) {
+    out[i] = tv.ctr->special_state == 1;
+    return;
+  }
+  const uint64_t hv = hash_key(id);
+  const uint64_t i1 = index_hash(tv.hp, hv);
+  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1);
+  int found = 0;
+  for (int s = 0; s < kSlots; ++s) {
+    found |= (tv.buckets[i1].key[s] == id);
+    found |= (tv.buckets[i2].key[s] == id);
+  }
+  out[i] = found;
+}
+}  // namespace mhte
+
+#include "mhte_touched_host.h"
 
 namespace mhte {
 
@@ -1637,6 +1673,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
     tb.upsert<OP>(id + id_split[i], num_ids, nullptr, value + value_offset, lrs, update_time, flags,
                   nullptr, S(stream));
     if (OP == kOpOptimize) tb.maybe_evict(S(stream));
+    if (OP == kOpOptimize) tk_record(t, tb, int32_t(i), id + id_split[i], num_ids, nullptr, S(stream));
     value_offset += value_size;
   }
 }
@@ -1649,9 +1686,23 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 
 struct mhte_multi_step {
   mhte::MultiStep ms;
+  // the touched-key set's segments over the tables' unique ids, per slot, built at creation: one insert
+  // call per backward however many tables there are
+  std::vector<mhte::TkDesc> h_tk[2];
+  mhte::TkDesc* d_tk = nullptr;   // [2][T]
+  std::vector<uint8_t> tk_skip;
+  ~mhte_multi_step() {
+    if (d_tk) {
+      (void)hipSetDevice(ms.device);
+      (void)hipDeviceSynchronize();
+      (void)hipFree(d_tk);
+    }
+  }
+  bool counted = false;   // in mhte_multi_table::multi_steps
 };
 struct mhte_shard_step {
   mhte::ShardStep ss;
+  bool counted = false;   // in mhte_multi_table::shard_steps
 };
 struct mhte_dense_mlp {
   mhte::DenseMlp m;
@@ -1712,6 +1763,16 @@ void mhte_multi_table_destroy(mhte_multi_table* t) {
       for (auto& tb : t->tables)
         if (tb->ext_flush) tb->finish_pending(nullptr);
     } catch (...) {
+    }
+    {
+      std::lock_guard<std::mutex> link(g_touched_link_mu);
+      if (t->touched) {
+        std::lock_guard<std::mutex> gs(t->touched->mu);
+        t->touched->owner = nullptr;
+        t->touched = nullptr;
+      }
+      for (mhte_multi_step* ms : t->multi_steps) ms->counted = false;
+      for (mhte_shard_step* ss : t->shard_steps) ss->counted = false;
     }
     std::lock_guard<std::mutex> g(g_registry_mu);
     auto it = g_registry.find(t->shared_name);
@@ -1828,6 +1889,7 @@ mhte_status mhte_reinitialize(mhte_multi_table* t, const char* table_name, const
     }
     std::lock_guard<std::mutex> g(tb.mu);
     tb.upsert<kOpReinit>(id, n, nullptr, nullptr, nullptr, now, 0, id_status, S(stream));
+    tk_record(t, tb, idx, id, n, nullptr, S(stream));
   });
 }
 
@@ -1932,6 +1994,9 @@ mhte_status mhte_fused_optimize(mhte_multi_table* t, const int64_t* ids,
       for (auto& tb : t->tables) locks.emplace_back(tb->mu);
       fused_optimize_segments(t, ids, fused_slot_size, id_grads, id_offsets, grad_offsets,
                               learning_rates, req_time, global_step, num_of_shards, S(stream));
+      for (int idx = 0; t->touched && idx < T * num_of_shards; ++idx)
+        tk_record(t, *t->tables[idx % T], idx % T, ids + id_offsets[idx], fused_slot_size[idx], nullptr,
+                  S(stream));
       return;
     }
     for (int s = 0; s < num_of_shards; ++s) {
@@ -1949,6 +2014,7 @@ mhte_status mhte_fused_optimize(mhte_multi_table* t, const int64_t* ids,
         tb.upsert<kOpOptimize>(ids + id_offsets[idx], n, nullptr, id_grads + grad_offsets[idx], lrs,
                                req_time, flags, nullptr, S(stream));
         if (s == num_of_shards - 1) tb.maybe_evict(S(stream));
+        tk_record(t, tb, k, ids + id_offsets[idx], n, nullptr, S(stream));
       }
     }
   });
@@ -1964,27 +2030,6 @@ mhte_status mhte_table_size(mhte_multi_table* t, int32_t table, int64_t* size, v
   });
 }
 
-namespace mhte {
-__global__ __launch_bounds__(256) void contains_kernel(TableView tv, const int64_t* __restrict__ ids,
-                                                       int64_t n, int32_t* __restrict__ out) {
-  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int64_t id = ids[i];
-  if (id == kEmptyKey) {
-    out[i] = tv.ctr->special_state == 1;
-    return;
-  }
-  const uint64_t hv = hash_key(id);
-  const uint64_t i1 = index_hash(tv.hp, hv);
-  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1);
-  int found = 0;
-  for (int s = 0; s < kSlots; ++s) {
-    found |= (tv.buckets[i1].key[s] == id);
-    found |= (tv.buckets[i2].key[s] == id);
-  }
-  out[i] = found;
-}
-}  // namespace mhte
 
 mhte_status mhte_table_contains(mhte_multi_table* t, int32_t table, const int64_t* id, int64_t n,
                                 int32_t* out, void* stream) {
@@ -1994,7 +2039,7 @@ mhte_status mhte_table_contains(mhte_multi_table* t, int32_t table, const int64_
     if (n <= 0) return;
     std::lock_guard<std::mutex> g(tb.mu);
     tb.finish_pending(S(stream));
-    contains_kernel<<<dim3(uint32_t((n + 255) / 256)), 256, 0, S(stream)>>>(tb.view, id, n, out);
+    contains_kernel<<<dim3(uint32_t((n + 255) / 256)), 256, 0, S(stream)>>>(tb.view, id, nullptr, n, out);
     HIP_OK(hipGetLastError());
   });
 }
@@ -2633,6 +2678,148 @@ mhte_status mhte_multi_table_set_filter(mhte_multi_table* t, mhte_hash_filter* f
       tb->flt_cap = f ? f->split_cap : 0;
       tb->flt_budget = f ? &f->budget : nullptr;
       tb->refresh_view();
+    }
+  });
+}
+
+// ---- touched-key set (mhte_touched_host.h) ---------------------------------------------------------
+mhte_status mhte_touched_key_set_create(int64_t capacity, int64_t max_insert, int32_t device,
+                                        mhte_touched_key_set** out) {
+  return guard([&] {
+    if (!out) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: null out");
+    if (capacity <= 0 || capacity > int64_t(1) << 30)
+      throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: capacity must be 1..2^30");
+    if (max_insert < 0) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: negative max_insert");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+      throw Error(MHTE_UNAVAILABLE, "no HIP device: the MI355X engine has no CPU fallback");
+    if (device < 0 || device >= ndev) throw Error(MHTE_INVALID_ARGUMENT, "device ordinal out of range");
+    HIP_OK(hipSetDevice(device));
+    std::unique_ptr<mhte_touched_key_set> s(new mhte_touched_key_set);
+    s->device = device;
+    s->capacity = capacity;
+    const int64_t limit = std::min<int64_t>(std::min<int64_t>(max_insert ? max_insert : capacity + 1, capacity + 1),
+                                            int64_t(kTkMaxPositions));
+    s->call_limit = uint32_t(limit);
+    const uint64_t nslots = uint64_t(1) << std::max<uint32_t>(8, ceil_log2(2 * uint64_t(capacity + 1 + limit)));
+    if (nslots > (uint64_t(1) << 31)) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: too large (more than 2^31 slots)");
+    HIP_OK(hipMalloc(&s->view.slots, nslots * sizeof(TkSlot)));
+    HIP_OK(hipMemset(s->view.slots, 0, nslots * sizeof(TkSlot)));
+    HIP_OK(hipMalloc(&s->view.ctl, sizeof(TkCtl)));
+    HIP_OK(hipMemset(s->view.ctl, 0, sizeof(TkCtl)));
+    const size_t words = size_t(limit + 31) / 32 + 1;
+    HIP_OK(hipMalloc(&s->view.bitmap, words * sizeof(uint32_t)));
+    HIP_OK(hipMemset(s->view.bitmap, 0, words * sizeof(uint32_t)));
+    s->view.mask = uint32_t(nslots - 1);
+    s->view.capacity = uint32_t(capacity);
+    HIP_OK(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    HIP_OK(hipDeviceSynchronize());
+    *out = s.release();
+  });
+}
+
+void mhte_touched_key_set_destroy(mhte_touched_key_set* set) {
+  if (!set) return;
+  {
+    std::lock_guard<std::mutex> link(g_touched_link_mu);
+    if (mhte_multi_table* t = set->owner) {
+      std::vector<std::unique_lock<std::mutex>> locks;
+      for (auto& tb : t->tables) locks.emplace_back(tb->mu);
+      t->touched = nullptr;
+      set->owner = nullptr;
+    }
+  }
+  delete set;
+}
+
+mhte_status mhte_touched_key_set_insert(mhte_touched_key_set* set, const int64_t* ids, int64_t n_max,
+                                        const uint32_t* n_dev, int32_t tag, void* stream) {
+  return guard([&] {
+    if (n_max < 0 || n_max > int64_t(0xffffffffu)) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: bad n_max");
+    if (!set) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: null handle");
+    if (tag < 0) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: negative tag");
+    if (n_max == 0) return;
+    if (!ids) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: null ids");
+    HIP_OK(hipSetDevice(set->device));
+    std::lock_guard<std::mutex> g(set->mu);
+    tk_enter_stream(*set, S(stream));
+    TkDesc d{};
+    d.ids = ids;
+    d.n_dev = n_dev;
+    d.n_max = uint32_t(n_max);
+    d.tag = tag;
+    tk_insert_segments(*set, &d, nullptr, 1, nullptr, S(stream));
+  });
+}
+
+mhte_status mhte_touched_key_set_stats(mhte_touched_key_set* set, int64_t out[4], void* stream) {
+  return guard([&] {
+    if (!set || !out) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: null argument");
+    HIP_OK(hipSetDevice(set->device));
+    std::lock_guard<std::mutex> g(set->mu);
+    tk_enter_stream(*set, S(stream));
+    TkCtl h;
+    HIP_OK(hipMemcpyAsync(&h, set->view.ctl, sizeof(h), hipMemcpyDeviceToHost, S(stream)));
+    HIP_OK(hipStreamSynchronize(S(stream)));
+    out[0] = int64_t(h.size);
+    out[1] = int64_t(h.dropped);
+    out[2] = int64_t(h.clears);
+    out[3] = set->capacity;
+  });
+}
+
+mhte_status mhte_touched_key_set_steal(mhte_touched_key_set* set, int64_t* ids_out, int32_t* tags_out,
+                                       int64_t cap, int64_t* n, void* stream) {
+  return guard([&] {
+    if (!set || !n) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: null argument");
+    if (cap < 0 || (cap > 0 && !ids_out)) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: bad output buffer");
+    HIP_OK(hipSetDevice(set->device));
+    std::lock_guard<std::mutex> g(set->mu);
+    hipStream_t st = S(stream);
+    tk_enter_stream(*set, st);
+    TkCtl h;
+    HIP_OK(hipMemcpyAsync(&h, set->view.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (int64_t(h.size) > cap)
+      throw Error(MHTE_INVALID_ARGUMENT, "touched-key set: the set holds " + std::to_string(h.size) +
+                                             " keys, the output buffers " + std::to_string(cap));
+    *n = int64_t(h.size);
+    if (h.size == 0) return;
+    const TkView v = set->view;
+    HIP_OK(hipMemsetAsync(&v.ctl->steal_n, 0, sizeof(uint32_t), st));
+    const uint32_t nb = uint32_t(std::min<uint64_t>((uint64_t(v.mask) + 1u) / kTkBlock, 2048));
+    tk_steal_kernel<<<nb, kTkBlock, 0, st>>>(v, ids_out, tags_out, uint32_t(std::min<int64_t>(cap, 0xffffffffll)));
+    tk_clear_kernel<<<nb, kTkBlock, 0, st>>>(v, 1);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(st));
+  });
+}
+
+mhte_status mhte_multi_table_set_touched_key_set(mhte_multi_table* t, mhte_touched_key_set* set) {
+  return guard([&] {
+    check_handle(t);
+    std::lock_guard<std::mutex> link(g_touched_link_mu);
+    if (set) {
+      if (set->device != t->device) throw Error(MHTE_INVALID_ARGUMENT, "touched-key set lives on another device");
+      if (set->owner && set->owner != t)
+        throw Error(MHTE_INVALID_ARGUMENT, "touched-key set is attached to another MultiHashTable");
+      if (!t->shard_steps.empty())
+        throw Error(MHTE_INVALID_ARGUMENT, "an id-sharded step exists on this MultiHashTable: it does not record "
+                                           "on the owner yet");
+      if (!t->multi_steps.empty() && tk_any_filter(t))
+        throw Error(MHTE_INVALID_ARGUMENT, "a multi step exists on this MultiHashTable and it has an admission "
+                                           "filter: the fused step cannot record what the filter admits");
+    }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (auto& tb : t->tables) locks.emplace_back(tb->mu);
+    if (t->touched && t->touched != set) {
+      std::lock_guard<std::mutex> gs(t->touched->mu);
+      t->touched->owner = nullptr;
+    }
+    t->touched = set;
+    if (set) {
+      std::lock_guard<std::mutex> gs(set->mu);
+      set->owner = t;
     }
   });
 }
@@ -3695,6 +3882,7 @@ mhte_status mhte_table_optimize_n(mhte_multi_table* t, int32_t table, const int6
     tb.upsert<kOpOptimize>(id, n_max, n_dev, value, learning_rate, update_time, flags, nullptr,
                            S(stream));
     tb.maybe_evict(S(stream));
+    tk_record(t, tb, table, id, n_max, n_dev, S(stream));
   });
 }
 
@@ -3736,6 +3924,7 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
       tb.ensure_capacity(uint64_t(n_max), st);
       tb.launch_upsert<kOpOptimize>(unique_ids, n_max, n_unique_dev, grads, list_start, seg_pos, a, nullptr, st);
       tb.maybe_evict(st);
+      tk_record(t, tb, table, unique_ids, n_max, n_unique_dev, st);
       return;
     }
     if (tb.fusable() && tb.basic_opts()) {   // (sum_apply_kernel is compiled for SGD / Adagrad / FTRL)
@@ -3743,6 +3932,7 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
                       seg_pos, n, grad_unique, learning_rate, update_time,
                       (flags & MHTE_EXACT_ORDER) != 0, (flags & MHTE_DEFER_SLOWPATH) != 0, st);
       if (!(flags & MHTE_DEFER_SLOWPATH)) tb.maybe_evict(st);
+      tk_record(t, tb, table, unique_ids, n_max, n_unique_dev, st);
       return;
     }
     // wide rows: segment sum, then the ordinary upsert over the unique ids (needs the CSR form of
@@ -3757,6 +3947,7 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
     if (s2 != MHTE_OK) throw Error(s2, g_last_error);
     tb.upsert<kOpOptimize>(unique_ids, n_max, n_unique_dev, grad_unique, learning_rate, update_time,
                            MHTE_IDS_UNIQUE, nullptr, st);
+    tk_record(t, tb, table, unique_ids, n_max, n_unique_dev, st);
   });
 }
 
@@ -3913,6 +4104,13 @@ mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, m
   return guard([&] {
     HostProfScope hps(1);
     Table& tb = table_at(t, table);
+    // (the lock first: the refusal below reads the attachment, and does not depend on the batch)
+    std::lock_guard<std::mutex> g(tb.mu);
+    hps.locked();
+    if (t->touched && tb.flt_slots)
+      throw Error(MHTE_INVALID_ARGUMENT, "step_backward: a table with an admission filter AND a touched-key set "
+                                         "takes the op-level update (mhte_table_sum_optimize_n): the fused step "
+                                         "decides admission inside its apply role");
     if (!ws || ws == ws_next)
       throw Error(MHTE_INVALID_ARGUMENT, "step_backward needs the batch's workspace, distinct "
                                          "from the next batch's");
@@ -3929,8 +4127,6 @@ mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, m
       throw Error(MHTE_INVALID_ARGUMENT, "step_backward: row too wide (or a whole-segment optimizer) "
                                          "for the fused step");
     HIP_OK(hipSetDevice(t->device));
-    std::lock_guard<std::mutex> g(tb.mu);
-    hps.locked();
     tb.note_update_time(update_time);
     RunView ahead{};
     if (ws_ahead)
@@ -3943,6 +4139,7 @@ mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, m
       tb.finish_pending(S(stream));
       tb.maybe_evict(S(stream));
     }
+    tk_record(t, tb, table, unique_ids, n_max, n_unique_dev, S(stream));
   });
 }
 
@@ -4799,14 +4996,45 @@ mhte_status mhte_multi_step_create(mhte_multi_table* t, int64_t max_batch_per_ta
     check_handle(t);
     if (!out) throw Error(MHTE_INVALID_ARGUMENT, "null out");
     HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> link(g_touched_link_mu);   // (before the tables', as everywhere)
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto& tb : t->tables) locks.emplace_back(tb->mu);
+    if (t->touched && tk_any_filter(t))
+      throw Error(MHTE_INVALID_ARGUMENT, "multi step: a MultiHashTable with an admission filter AND a touched-key "
+                                         "set takes the op-level update: the fused step decides admission inside "
+                                         "its apply role");
     std::unique_ptr<mhte_multi_step> s(new mhte_multi_step);
     s->ms.init(t, max_batch_per_table);
+    const uint32_t T = s->ms.T;
+    for (int sl = 0; sl < 2; ++sl) {
+      s->h_tk[sl].assign(T, TkDesc{});
+      for (uint32_t k = 0; k < T; ++k) {
+        TkDesc& d = s->h_tk[sl][k];
+        d.ids = s->ms.h_st[k].rv[sl].uids;
+        d.n_dev = s->ms.h_st[k].rv[sl].n_unique;
+        d.n_max = uint32_t(max_batch_per_table);
+        d.tag = int32_t(k);
+      }
+    }
+    HIP_OK(hipMalloc(&s->d_tk, sizeof(TkDesc) * 2 * T));
+    for (int sl = 0; sl < 2; ++sl)
+      HIP_OK(hipMemcpy(s->d_tk + size_t(sl) * T, s->h_tk[sl].data(), sizeof(TkDesc) * T, hipMemcpyHostToDevice));
+    s->tk_skip.assign(T, 0);
+    t->multi_steps.push_back(s.get());   // (behind the last call that can throw)
+    s->counted = true;
     *out = s.release();
   });
 }
-void mhte_multi_step_destroy(mhte_multi_step* s) { delete s; }
+void mhte_multi_step_destroy(mhte_multi_step* s) {
+  if (s) {
+    std::lock_guard<std::mutex> link(g_touched_link_mu);
+    if (s->counted) {   // (false once the table went first: mhte_multi_table_destroy unlinks)
+      auto& v = s->ms.mt->multi_steps;
+      v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    }
+  }
+  delete s;
+}
 
 mhte_status mhte_multi_step_forward(mhte_multi_step* s, const int64_t* id, const int64_t* id_split,
                                     int64_t n_split, float* embedding, int64_t embedding_len,
@@ -4831,8 +5059,19 @@ mhte_status mhte_multi_step_backward(mhte_multi_step* s, const float* value, int
     HIP_OK(hipSetDevice(s->ms.device));
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto& tb : s->ms.mt->tables) locks.emplace_back(tb->mu);
+    mhte_touched_key_set* set = s->ms.mt->touched;
+    if (set && tk_any_filter(s->ms.mt))
+      throw Error(MHTE_INVALID_ARGUMENT, "multi step: an admission filter AND a touched-key set are attached");
+    const int slot = s->ms.cur;
     s->ms.backward(value, value_len, learning_rate, n_learning_rate, update_time,
                    (flags & MHTE_EXACT_ORDER) != 0, S(stream), global_step);
+    if (set) {
+      const uint32_t T = s->ms.T;
+      for (uint32_t k = 0; k < T; ++k) s->tk_skip[k] = s->ms.n_slot[slot][k] ? 0 : 1;
+      std::lock_guard<std::mutex> g(set->mu);
+      tk_enter_stream(*set, S(stream));
+      tk_insert_segments(*set, s->h_tk[slot].data(), s->d_tk + size_t(slot) * T, T, s->tk_skip.data(), S(stream));
+    }
   });
 }
 
@@ -4879,14 +5118,29 @@ mhte_status mhte_shard_step_create(mhte_multi_table* t, int64_t max_batch_per_ta
     check_handle(t);
     if (!out) throw Error(MHTE_INVALID_ARGUMENT, "null out");
     HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> link(g_touched_link_mu);   // (before the tables', as everywhere)
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto& tb : t->tables) locks.emplace_back(tb->mu);
     std::unique_ptr<mhte_shard_step> s(new mhte_shard_step);
+    if (t->touched)
+      throw Error(MHTE_INVALID_ARGUMENT, "shard step: the MultiHashTable has a touched-key set attached; the "
+                                         "id-sharded step does not record on the owner yet");
     s->ss.init(t, max_batch_per_table, rank, world, ids_per_peer_table, unique_id);
+    t->shard_steps.push_back(s.get());
+    s->counted = true;
     *out = s.release();
   });
 }
-void mhte_shard_step_destroy(mhte_shard_step* s) { delete s; }
+void mhte_shard_step_destroy(mhte_shard_step* s) {
+  if (s) {
+    std::lock_guard<std::mutex> link(g_touched_link_mu);
+    if (s->counted) {
+      auto& v = s->ss.mt->shard_steps;
+      v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    }
+  }
+  delete s;
+}
 
 mhte_status mhte_shard_step_create_ipc(mhte_multi_table* t, int64_t max_batch_per_table, int32_t rank,
                                        int32_t world, int64_t ids_per_peer_table,
@@ -4895,10 +5149,16 @@ mhte_status mhte_shard_step_create_ipc(mhte_multi_table* t, int64_t max_batch_pe
     check_handle(t);
     if (!out) throw Error(MHTE_INVALID_ARGUMENT, "null out");
     HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> link(g_touched_link_mu);   // (before the tables', as everywhere)
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto& tb : t->tables) locks.emplace_back(tb->mu);
     std::unique_ptr<mhte_shard_step> s(new mhte_shard_step);
+    if (t->touched)
+      throw Error(MHTE_INVALID_ARGUMENT, "shard step: the MultiHashTable has a touched-key set attached; the "
+                                         "id-sharded step does not record on the owner yet");
     s->ss.init(t, max_batch_per_table, rank, world, ids_per_peer_table, nullptr, true);
+    t->shard_steps.push_back(s.get());
+    s->counted = true;
     *out = s.release();
   });
 }

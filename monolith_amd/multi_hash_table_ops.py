@@ -497,6 +497,30 @@ class MultiHashTable:
       k += int(m)
     return {k_: v for k_, v in out.items() if k_ in slot_to_id}
 
+  def set_touched_key_set(self, tks) -> "MultiHashTable":
+    """multi_hash_table_op.cc:94 (SetTouchedKeySet on every table): from here on the update paths record
+    (id, table) into ``tks`` (a touched_key_set_ops.TouchedKeySet); ``None`` detaches."""
+    check(self._lib.mhte_multi_table_set_touched_key_set(
+        self._h, tks.handle if tks is not None else C.c_void_p(0)))
+    self._touched_key_set = tks   # (kept alive with the table)
+    return self
+
+  def touched_entries(self) -> Dict[str, Tuple[torch.Tensor, List[bytes]]]:
+    """The body of ParameterSyncClientTfBridge::Push without the RPC (parameter_sync_tf_bridge.cc:70-90):
+    steals the attached set, groups the keys by table and looks up each table's EntryDumps ->
+    {name: (ids, [serialized EntryDump])} for the tables that have touched keys."""
+    tks = getattr(self, "_touched_key_set", None)
+    if tks is None:
+      raise _lib.MhteError(_lib.MHTE_FAILED_PRECONDITION, "no touched-key set is attached")
+    ids, tags = tks.steal_pairs()
+    by_table = {}
+    for i, name in enumerate(self._table_names):
+      sel = ids[tags == i]
+      if sel.numel():
+        by_table[name] = sel
+    entries = self.lookup_entry(by_table) if by_table else {}
+    return {name: (by_table[name], entries[name]) for name in by_table}
+
   def save_as_tensor(self, name_or_idx, shard_idx: int, num_shards: int, limit: int,
                      offset: int) -> Tuple[int, List[bytes]]:
     """MonolithHashTableSaveAsTensor (hash_table_ops.py:335-361 of the reference): up to ``limit``
