@@ -1,15 +1,18 @@
 """ctypes binding of libmhte.so (include/monolith_amd_hash_table.h).  Fails loudly when the HIP
 extension is missing: the product has no CPU or PyTorch fallback."""
 import ctypes as C
+import functools
 import os
+import re
 import subprocess
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libmhte.so")
 _SRC = os.path.join(_DIR, "csrc", "mhte.hip")
+_HEADER = os.path.join(_DIR, "..", "include", "monolith_amd_hash_table.h")
 # every header under csrc/ (a new one must not leave a stale library looking current)
 _DEPS = [_SRC] + sorted(os.path.join(_DIR, "csrc", h) for h in os.listdir(os.path.join(_DIR, "csrc"))
-                        if h.endswith(".h")) + [os.path.join(_DIR, "..", "include", "monolith_amd_hash_table.h")]
+                        if h.endswith(".h")) + [_HEADER]
 # A/B measurements: MHTE_LIBRARY=<other build of libmhte.so> (same ABI) is loaded instead
 _OVERRIDE = os.environ.get("MHTE_LIBRARY")
 
@@ -26,7 +29,6 @@ MHTE_SUM_DUPLICATES = 2
 MHTE_EXACT_ORDER = 1       # flags of mhte_table_sum_optimize_n
 MHTE_DEFER_SLOWPATH = 2
 MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS = 1
-ABI_VERSION = 19           # MHTE_ABI_VERSION of include/monolith_amd_hash_table.h
 
 OPT_SGD, OPT_ADAGRAD, OPT_FTRL = 0, 1, 2
 OPT_MOMENTUM, OPT_ADADELTA, OPT_RMSPROP, OPT_RMSPROPV2, OPT_ADAM, OPT_AMSGRAD = 3, 4, 5, 6, 7, 8
@@ -80,6 +82,73 @@ class TableStats(C.Structure):
               ("lookup_hits", C.c_int64), ("dropped", C.c_int64), ("evicted", C.c_int64),
               ("max_update_ts", C.c_int64), ("bytes_buckets", C.c_int64),
               ("bytes_rows", C.c_int64)]
+
+
+# ---- the binding, read from the header: it is the description of the ABI ----------------------
+_HEADER_TEXT = open(_HEADER).read()
+ABI_VERSION = int(re.search(r"^#define\s+MHTE_ABI_VERSION\s+(\d+)", _HEADER_TEXT, re.M).group(1))
+
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
+            "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double,
+            "mhte_status": C.c_int32}
+# the structs Python mirrors: a pointer to another struct is a type error at the call
+_MIRRORS = {"mhte_table_config": TableConfig, "mhte_layout_slice": LayoutSlice,
+            "mhte_table_stats": TableStats}
+_TYPE_RE = re.compile(r"(const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)?\s*(\[\d*\])?")
+
+
+def _ctype(spelling, decl, is_return=False):
+  """One return or parameter type as the header spells it -> its ctypes type."""
+  m = _TYPE_RE.fullmatch(spelling.strip())
+  if m:
+    const, base, stars, name, array = m.groups()
+    depth = stars.count("*") + (1 if array else 0)
+    if bool(name) != is_return:   # (parameters are named, a return type is a type alone)
+      if depth == 0 and (base in _SCALARS or (base == "void" and is_return)):
+        return _SCALARS.get(base)   # (None: returns void)
+      if depth == 1 and base == "char" and const and not array:
+        return C.c_char_p
+      if depth == 1 and base in _MIRRORS:
+        return C.POINTER(_MIRRORS[base])
+      if depth and (base in _SCALARS or base in ("void", "char") or base.startswith("mhte_")):
+        return C.c_void_p
+  raise MhteError(MHTE_INTERNAL, "monolith_amd_hash_table.h: cannot bind the type '%s' of '%s'" %
+                  (" ".join(spelling.split()), " ".join(decl.split())))
+
+
+@functools.lru_cache(maxsize=None)
+def signatures():
+  """{name: (restype, [argtypes])} of every function include/monolith_amd_hash_table.h declares."""
+  src = re.sub(r"/\*.*?\*/", " ", _HEADER_TEXT, flags=re.S)   # comments
+  src = re.sub(r"^\s*#.*$", "", src, flags=re.M)               # preprocessor lines
+  src = re.sub(r"\{[^{}]*\}", "", src)                         # enum and struct bodies
+  sigs = {}
+  for decl in src.split(";"):
+    if "(" not in decl:   # typedefs, enums, the extern "C" braces
+      continue
+    m = re.fullmatch(r"\s*([\w\s*]+?)\b(mhte_\w+)\s*\(([^()]*)\)\s*", decl)
+    if not m or m.group(2) in sigs:
+      raise MhteError(MHTE_INTERNAL, "monolith_amd_hash_table.h: cannot bind the declaration '%s'" %
+                      " ".join(decl.split()))
+    ret, name, params = m.groups()
+    params = [] if params.strip() == "void" else params.split(",")
+    sigs[name] = (_ctype(ret, decl, is_return=True), [_ctype(p, decl) for p in params])
+  return sigs
+
+
+EXPORTS = sorted(signatures())   # every symbol the header declares
+
+
+def bind(L, only_present=False):
+  """Types every declared function of the CDLL ``L``; ``only_present``: ``L`` holds part of the surface."""
+  for name, (restype, argtypes) in signatures().items():
+    if not hasattr(L, name):
+      if only_present:
+        continue
+      raise MhteError(MHTE_INTERNAL, "libmhte.so does not export %s" % name)
+    f = getattr(L, name)
+    f.restype, f.argtypes = restype, argtypes
+  return L
 
 
 def library_path():
@@ -140,9 +209,6 @@ _EAGER_SO = os.path.join(_DIR, "libmhte_eager.so")
 _EAGER_SRC = os.path.join(_DIR, "csrc", "eager_loop.c")
 
 
-_HEADER = os.path.join(_DIR, "..", "include", "monolith_amd_hash_table.h")
-
-
 def _try_build_eager_loop(verbose=False):
   """The helper is a benchmark aid: its build must not make the engine unavailable — a
   failure is reported and eager_lib() tries again when the helper is asked for."""
@@ -185,43 +251,6 @@ def eager_lib():
   return _eager
 
 
-# every symbol include/monolith_amd_hash_table.h declares
-EXPORTS = [
-    "mhte_last_error", "mhte_abi_version", "mhte_multi_table_create", "mhte_multi_table_destroy",
-    "mhte_num_tables", "mhte_table_name", "mhte_table_dim", "mhte_table_slice_size",
-    "mhte_table_index", "mhte_shared_name", "mhte_lookup", "mhte_optimize", "mhte_assign",
-    "mhte_assign_add", "mhte_reinitialize", "mhte_compute_fused_offsets", "mhte_fused_lookup",
-    "mhte_fused_optimize", "mhte_table_size", "mhte_table_contains", "mhte_table_evict",
-    "mhte_table_get_stats", "mhte_table_dump", "mhte_table_row_floats", "mhte_dedup_ws_create",
-    "mhte_dedup_ws_destroy", "mhte_unique", "mhte_gather_rows", "mhte_segment_sum",
-    "mhte_table_lookup_n", "mhte_table_optimize_n", "mhte_value_offsets",
-    "mhte_fill_with_offset_map", "mhte_fill_with_offset_map_gradient", "mhte_table_set_count_hits",
-    "mhte_table_sum_optimize_n", "mhte_unique_unordered", "mhte_table_fused_backward_ok", "mhte_table_finish_pending",
-    "mhte_table_step_forward", "mhte_table_step_backward", "mhte_table_step_backward_ahead", "mhte_profile_arm", "mhte_profile_read",
-    "mhte_trace_begin", "mhte_trace_end", "mhte_step_dedup", "mhte_shard_partition",
-    "mhte_step_scatter", "mhte_step_sum", "mhte_multi_table_save", "mhte_multi_table_restore", "mhte_table_save", "mhte_table_restore", "mhte_table_clear",
-    "mhte_hash_filter_create", "mhte_hash_filter_destroy", "mhte_multi_table_set_filter",
-    "mhte_hash_filter_get", "mhte_hash_filter_stats", "mhte_hash_filter_create_probabilistic", "mhte_fused_gather_embeddings_by_input",
-    "mhte_fused_gather_embeddings_by_input_gradient", "mhte_reduce_rows",
-    "mhte_multi_step_create", "mhte_multi_step_destroy", "mhte_multi_step_forward",
-    "mhte_multi_step_backward", "mhte_multi_step_unique_counts",
-    "mhte_shard_unique_id", "mhte_shard_step_create", "mhte_shard_step_destroy",
-    "mhte_shard_step_create_ipc", "mhte_shard_step_ipc_handle", "mhte_shard_step_ipc_connect",
-    "mhte_shard_step_ipc_selftest", "mhte_shard_step_set_overlap", "mhte_shard_step_set_grad_bits", "mhte_shard_step_set_exact_order", "mhte_shard_step_forward", "mhte_shard_step_backward", "mhte_shard_step_check",
-    "mhte_shard_step_info", "mhte_shard_step_launches", "mhte_shard_step_wire_stats", "mhte_shard_step_comm_ranks", "mhte_shard_step_unique_counts", "mhte_shard_group_forward", "mhte_shard_group_backward",
-    "mhte_multi_table_create_from_proto", "mhte_multi_table_find", "mhte_multi_table_is_initialized",
-    "mhte_hash_filter_create_from_proto", "mhte_lookup_entry", "mhte_feature_stat",
-    "mhte_table_save_as_tensor", "mhte_lookup_gradient",
-    "mhte_advance_clock_for_testing", "mhte_hash_filter_save", "mhte_hash_filter_restore",
-    "mhte_embedding_to_layout", "mhte_embedding_to_layout_grad",
-    "mhte_dense_mlp_create", "mhte_dense_mlp_destroy", "mhte_dense_mlp_set_params",
-    "mhte_dense_mlp_get_params", "mhte_dense_mlp_forward", "mhte_dense_mlp_backward",
-    "mhte_dense_mlp_launch_counts",
-    "mhte_fused_reduce_and_split", "mhte_fused_reduce_and_split_grad",
-    "mhte_touched_key_set_create", "mhte_touched_key_set_destroy", "mhte_touched_key_set_insert",
-    "mhte_touched_key_set_stats", "mhte_touched_key_set_steal", "mhte_multi_table_set_touched_key_set",
-]
-
 _lib = None
 
 
@@ -245,38 +274,7 @@ def lib():
                         "fallback path (MHTE_NO_REBUILD=1 loads an existing library as it is)" %
                         ("older than its sources" if os.path.exists(_SO) else "missing", e))
     L = C.CDLL(_OVERRIDE or _SO)
-    for name in EXPORTS:
-      if not hasattr(L, name):
-        raise MhteError(MHTE_INTERNAL, "libmhte.so does not export %s" % name)
-    L.mhte_last_error.restype = C.c_char_p
-    for name in ("mhte_table_name", "mhte_shared_name"):
-      getattr(L, name).restype = C.c_char_p
-    L.mhte_multi_table_destroy.restype = None
-    L.mhte_dedup_ws_destroy.restype = None
-    L.mhte_hash_filter_destroy.restype = None
-    L.mhte_multi_table_find.restype = C.c_void_p
-    L.mhte_multi_table_find.argtypes = [C.c_char_p]
-    L.mhte_multi_table_is_initialized.argtypes = [C.c_char_p]
-    L.mhte_advance_clock_for_testing.restype = None
-    L.mhte_advance_clock_for_testing.argtypes = [C.c_double]
-    L.mhte_multi_step_destroy.restype = None
-    L.mhte_multi_step_destroy.argtypes = [C.c_void_p]
-    L.mhte_shard_step_destroy.restype = None
-    L.mhte_shard_step_destroy.argtypes = [C.c_void_p]
-    L.mhte_dense_mlp_destroy.restype = None
-    L.mhte_dense_mlp_destroy.argtypes = [C.c_void_p]
-    L.mhte_hash_filter_destroy.argtypes = [C.c_void_p]
-    L.mhte_multi_table_destroy.argtypes = [C.c_void_p]
-    L.mhte_dedup_ws_destroy.argtypes = [C.c_void_p]
-    L.mhte_touched_key_set_destroy.restype = None
-    L.mhte_touched_key_set_destroy.argtypes = [C.c_void_p]
-    for name in ("mhte_num_tables",):
-      getattr(L, name).argtypes = [C.c_void_p]
-    for name in ("mhte_table_name", "mhte_table_dim", "mhte_table_slice_size",
-                 "mhte_table_row_floats", "mhte_table_fused_backward_ok"):
-      getattr(L, name).argtypes = [C.c_void_p, C.c_int32]
-    L.mhte_table_index.argtypes = [C.c_void_p, C.c_char_p]
-    L.mhte_shared_name.argtypes = [C.c_void_p]
+    bind(L)
     if L.mhte_abi_version() != ABI_VERSION:
       raise MhteError(MHTE_INTERNAL, "libmhte.so ABI version mismatch")
     _lib = L
@@ -315,23 +313,23 @@ TRACE_ROLES = {3: "run_dedup", 4: "displacement", 5: "lookup", 6: "work_list", 7
 
 def profile_arm(n):
   """Kernel-exact timing of the next ``n`` hot launches of this thread (mhte_profile_arm)."""
-  check(lib().mhte_profile_arm(C.c_int32(int(n))))
+  check(lib().mhte_profile_arm(int(n)))
 
 
 def profile_read(cap=65536):
   """-> [(kernel name, microseconds)] of the launches recorded since profile_arm; disarms."""
   tags = (C.c_int32 * cap)()
   us = (C.c_float * cap)()
-  n = C.c_int32(0)
-  check(lib().mhte_profile_read(C.c_int32(cap), tags, us, C.byref(n)))
-  m = min(cap, n.value)
+  n = (C.c_int32 * 1)()
+  check(lib().mhte_profile_read(cap, tags, us, n))
+  m = min(cap, n[0])
   return [(PROFILE_TAGS.get(tags[i], str(tags[i])), float(us[i])) for i in range(m)]
 
 
 def trace_begin(buf, cap_records):
   """Per-wavefront timeline of the step kernels into ``buf`` (uint64 cuda tensor, TRACE_WORDS
   words per record) — mhte_trace_begin."""
-  check(lib().mhte_trace_begin(vp(buf), C.c_int64(int(cap_records))))
+  check(lib().mhte_trace_begin(vp(buf), int(cap_records)))
 
 
 def trace_end(cap=4096):
@@ -340,7 +338,7 @@ def trace_end(cap=4096):
   grid = (C.c_int32 * cap)()
   block = (C.c_int32 * cap)()
   off = (C.c_int64 * cap)()
-  n = C.c_int32(0)
-  check(lib().mhte_trace_end(C.c_int32(cap), tag, grid, block, off, C.byref(n)))
-  m = min(cap, n.value)
+  n = (C.c_int32 * 1)()
+  check(lib().mhte_trace_end(cap, tag, grid, block, off, n))
+  m = min(cap, n[0])
   return [(PROFILE_TAGS.get(tag[i], str(tag[i])), grid[i], block[i], off[i]) for i in range(m)]

@@ -24,14 +24,12 @@ class DenseMlp:
     self._lib = _lib.lib()
     import os
     if os.environ.get("MHTE_DENSE_LIBRARY"):   # development builds of the tower alone (scripts/dbg/gemm_dev.hip)
-      self._lib = C.CDLL(os.environ["MHTE_DENSE_LIBRARY"])
-      self._lib.mhte_dense_mlp_destroy.restype = None
-      self._lib.mhte_dense_mlp_destroy.argtypes = [C.c_void_p]
+      self._lib = _lib.bind(C.CDLL(os.environ["MHTE_DENSE_LIBRARY"]), only_present=True)
     self._device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     arr = (C.c_int32 * len(self.widths))(*self.widths)
     h = C.c_void_p()
-    _lib.check(self._lib.mhte_dense_mlp_create(arr, C.c_int32(len(self.widths)), C.c_int64(self.max_batch),
-                                               C.c_int32(self._device.index), C.byref(h)))
+    _lib.check(self._lib.mhte_dense_mlp_create(arr, len(self.widths), self.max_batch, self._device.index,
+                                               C.byref(h)))
     self._h = h
     self._batch = 0
 
@@ -47,14 +45,14 @@ class DenseMlp:
     w = weight.detach().to(self._device, torch.float32).contiguous()
     b = bias.detach().to(self._device, torch.float32).contiguous()
     assert w.numel() == self.widths[layer] * self.widths[layer + 1] and b.numel() == self.widths[layer + 1]
-    _lib.check(self._lib.mhte_dense_mlp_set_params(self._h, C.c_int32(layer), _lib.vp(w), _lib.vp(b),
+    _lib.check(self._lib.mhte_dense_mlp_set_params(self._h, layer, _lib.vp(w), _lib.vp(b),
                                                    self._stream()))
     torch.cuda.current_stream(self._device).synchronize()   # (w, b may be temporaries)
 
   def get_params(self, layer):
     w = torch.empty(self.widths[layer + 1], self.widths[layer], dtype=torch.float32, device=self._device)
     b = torch.empty(self.widths[layer + 1], dtype=torch.float32, device=self._device)
-    _lib.check(self._lib.mhte_dense_mlp_get_params(self._h, C.c_int32(layer), _lib.vp(w), _lib.vp(b),
+    _lib.check(self._lib.mhte_dense_mlp_get_params(self._h, layer, _lib.vp(w), _lib.vp(b),
                                                    self._stream()))
     return w, b
 
@@ -62,7 +60,7 @@ class DenseMlp:
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == self.widths[0]
     B = x.shape[0]
     y = out if out is not None else torch.empty(B, dtype=torch.float32, device=self._device)
-    _lib.check(self._lib.mhte_dense_mlp_forward(self._h, _lib.vp(x), C.c_int64(B), _lib.vp(y), self._stream()))
+    _lib.check(self._lib.mhte_dense_mlp_forward(self._h, _lib.vp(x), B, _lib.vp(y), self._stream()))
     self._batch = B
     self._keep = x
     return y
@@ -73,8 +71,7 @@ class DenseMlp:
     if need_dx:
       dx = out if out is not None else torch.empty(self._batch, self.widths[0], dtype=torch.float32,
                                                    device=self._device)
-    _lib.check(self._lib.mhte_dense_mlp_backward(self._h, _lib.vp(dy), _lib.vp(dx), C.c_float(float(lr)),
-                                                 self._stream()))
+    _lib.check(self._lib.mhte_dense_mlp_backward(self._h, _lib.vp(dy), _lib.vp(dx), lr, self._stream()))
     return dx
 
   GEMM_ROLES = ("forward", "dgrad", "dgrad_input", "wgrad")

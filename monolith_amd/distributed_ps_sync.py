@@ -134,8 +134,7 @@ class ShardedMultiStep:
         uid = shard_unique_id()
     h = C.c_void_p()
     _lib.check(self._lib.mhte_shard_step_create(
-        table.handle, C.c_int64(self.batch), C.c_int32(self.rank), C.c_int32(self.world),
-        C.c_int64(int(ids_per_peer_table)), uid, C.byref(h)))
+        table.handle, self.batch, self.rank, self.world, int(ids_per_peer_table), uid, C.byref(h)))
     self._h = h
     self._ahead = None
     self._keep = None
@@ -160,12 +159,11 @@ class ShardedMultiStep:
     blob = C.create_string_buffer(128)
     try:
       _lib.check(self._lib.mhte_shard_step_create_ipc(
-          self.table.handle, C.c_int64(self.batch), C.c_int32(self.rank), C.c_int32(self.world),
-          C.c_int64(int(ids_per_peer_table)), C.byref(h)))
+          self.table.handle, self.batch, self.rank, self.world, int(ids_per_peer_table), C.byref(h)))
       if self._grad_fp16 is not None:
-        _lib.check(self._lib.mhte_shard_step_set_grad_bits(h, C.c_int32(16 if self._grad_fp16 else 32)))
+        _lib.check(self._lib.mhte_shard_step_set_grad_bits(h, 16 if self._grad_fp16 else 32))
       if self._overlap is not None:
-        _lib.check(self._lib.mhte_shard_step_set_overlap(h, C.c_int32(1 if self._overlap else 0)))
+        _lib.check(self._lib.mhte_shard_step_set_overlap(h, self._overlap))
       _lib.check(self._lib.mhte_shard_step_ipc_handle(h, blob))
     except _lib.MhteError as e:
       err = e
@@ -176,7 +174,7 @@ class ShardedMultiStep:
       blobs[0] = blob.raw if err is None else None
     if err is None and all(b is not None for b in blobs):
       try:
-        _lib.check(self._lib.mhte_shard_step_ipc_connect(h, b"".join(blobs), C.c_int32(self.world)))
+        _lib.check(self._lib.mhte_shard_step_ipc_connect(h, b"".join(blobs), self.world))
       except _lib.MhteError as e:
         err = e
     elif err is None:
@@ -218,18 +216,18 @@ class ShardedMultiStep:
   def set_overlap(self, on: bool = True):
     """The next batch's dedup / numbering / id dispatch on a stream of the step's own, beside the
     dense model the caller runs between ``forward`` and ``backward`` (mhte_shard_step_set_overlap)."""
-    self._libmod.check(self._lib.mhte_shard_step_set_overlap(self._h, C.c_int32(1 if on else 0)))
+    self._libmod.check(self._lib.mhte_shard_step_set_overlap(self._h, on))
     return self
 
   def set_exact_order(self, on: bool = True):
     """Every duplicate list of this rank summed strictly in occurrence order (mhte_shard_step_set_exact_order):
     the owners' rows are then the reference's bit for bit.  Takes effect at the next backward."""
-    self._libmod.check(self._lib.mhte_shard_step_set_exact_order(self._h, C.c_int32(1 if on else 0)))
+    self._libmod.check(self._lib.mhte_shard_step_set_exact_order(self._h, on))
 
   def set_grad_fp16(self, on: bool = True):
     """The gradient exchange in fp16 (mhte_shard_step_set_grad_bits; the reference's optional cast of
     the gradient all-to-all): a numerics change, every rank must choose the same."""
-    self._libmod.check(self._lib.mhte_shard_step_set_grad_bits(self._h, C.c_int32(16 if on else 32)))
+    self._libmod.check(self._lib.mhte_shard_step_set_grad_bits(self._h, 16 if on else 32))
     return self
 
   def info(self):
@@ -285,9 +283,8 @@ class ShardedMultiStep:
     else:
       nv, nsp_p, nsp_n = C.c_void_p(0), None, 0
     _lib.check(self._lib.mhte_shard_step_forward(
-        self._h, _lib.vp(ragged.values), sp.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(sp.size),
-        _lib.vp(out), C.c_int64(out.numel()), nv, nsp_p, C.c_int64(nsp_n),
-        C.c_int32(1 if pre else 0), self._stream()))
+        self._h, _lib.vp(ragged.values), sp.ctypes.data_as(C.POINTER(C.c_int64)), sp.size,
+        _lib.vp(out), out.numel(), nv, nsp_p, nsp_n, pre, self._stream()))
     self._ahead = self._key(next_ragged) if next_ragged is not None else None
     self._keep = (ragged, next_ragged, out)
     return out
@@ -296,9 +293,8 @@ class ShardedMultiStep:
     _lib = self._libmod
     lrs = np.ascontiguousarray(self.table.learning_rate, dtype=np.float32)
     _lib.check(self._lib.mhte_shard_step_backward(
-        self._h, _lib.vp(flat_grad), C.c_int64(flat_grad.numel()),
-        lrs.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(lrs.size), C.c_int64(int(update_time)),
-        C.c_int64(int(global_step)), self._stream()))
+        self._h, _lib.vp(flat_grad), flat_grad.numel(), lrs.ctypes.data_as(C.POINTER(C.c_float)),
+        lrs.size, int(update_time), int(global_step), self._stream()))
 
   def unique_counts(self) -> np.ndarray:
     """Distinct ids per table of the batch last given to ``forward`` (synchronises)."""
@@ -327,8 +323,7 @@ class ShardedStepGroup:
     for r, t in enumerate(self.tables):
       h = C.c_void_p()
       _lib.check(self._lib.mhte_shard_step_create(
-          t.handle, C.c_int64(int(batch_per_table)), C.c_int32(r), C.c_int32(self.world),
-          C.c_int64(int(ids_per_peer_table)), None, C.byref(h)))
+          t.handle, int(batch_per_table), r, self.world, int(ids_per_peer_table), None, C.byref(h)))
       self._hs.append(h)
     self._arr = (C.c_void_p * self.world)(*[h.value for h in self._hs])
     self._keep = None
@@ -359,7 +354,7 @@ class ShardedStepGroup:
   def set_exact_order(self, on: bool = True):
     """Every rank's duplicate lists summed strictly in occurrence order (mhte_shard_step_set_exact_order)."""
     for h in self._hs:
-      self._libmod.check(self._lib.mhte_shard_step_set_exact_order(h, C.c_int32(1 if on else 0)))
+      self._libmod.check(self._lib.mhte_shard_step_set_exact_order(h, on))
 
   def wire_stats(self):
     """Per rank: mhte_shard_step_wire_stats of the last forward + backward (device copies stand for the pairs)."""
@@ -392,8 +387,7 @@ class ShardedStepGroup:
     else:
       nsps, nids, nspl, n_next = None, None, None, 0
     _lib.check(self._lib.mhte_shard_group_forward(
-        self._arr, C.c_int32(N), ids, spl, C.c_int64(sps[0].size), emb, elen, nids, nspl,
-        C.c_int64(n_next), C.c_int32(1 if prefetched else 0),
+        self._arr, N, ids, spl, sps[0].size, emb, elen, nids, nspl, n_next, prefetched,
         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     self._keep = (raggeds, next_raggeds, outs, sps, nsps)
     return outs
@@ -404,8 +398,8 @@ class ShardedStepGroup:
     val = (C.c_void_p * N)(*[g.data_ptr() for g in flat_grads])
     vlen = (C.c_int64 * N)(*[g.numel() for g in flat_grads])
     _lib.check(self._lib.mhte_shard_group_backward(
-        self._arr, C.c_int32(N), val, vlen, lrs.ctypes.data_as(C.POINTER(C.c_float)),
-        C.c_int64(lrs.size), C.c_int64(int(update_time)), C.c_int64(int(global_step)),
+        self._arr, N, val, vlen, lrs.ctypes.data_as(C.POINTER(C.c_float)), lrs.size,
+        int(update_time), int(global_step),
         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
   def check(self):

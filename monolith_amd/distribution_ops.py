@@ -40,7 +40,7 @@ class DedupWorkspace:
     self._lib = _lib.lib()
     self._device = torch.cuda.current_device() if device is None else int(device)
     h = C.c_void_p()
-    check(self._lib.mhte_dedup_ws_create(C.c_int32(self._device), C.byref(h)))
+    check(self._lib.mhte_dedup_ws_create(self._device, C.byref(h)))
     self._h = h
 
   def close(self):
@@ -69,19 +69,19 @@ class DedupWorkspace:
       nu = torch.zeros(1, dtype=torch.int32, device=dev)
     else:
       uids, inverse, seg_off, seg_pos, nu = out[:5]
-    host = C.c_int64(0)
-    check(self._lib.mhte_unique(self._h, vp(ids), C.c_int64(n), vp(uids), vp(inverse), vp(seg_off),
-                                vp(seg_pos), vp(nu), C.byref(host) if want_host_count else None,
+    host = (C.c_int64 * 1)()
+    check(self._lib.mhte_unique(self._h, vp(ids), n, vp(uids), vp(inverse), vp(seg_off),
+                                vp(seg_pos), vp(nu), host if want_host_count else None,
                                 _stream()))
     return UniqueResult(uids, inverse, seg_off, seg_pos, nu,
-                        int(host.value) if want_host_count else None)
+                        host[0] if want_host_count else None)
 
   def step_dedup(self, ids: torch.Tensor, uids: torch.Tensor, n_unique_dev: torch.Tensor):
     """Run dedup of the FIRST batch of a pipelined step (mhte_step_dedup): unique ids in
     unspecified order + count on the device; the occurrence runs stay in this workspace for
     ``MultiHashTable.table_step_backward``."""
     assert ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous()
-    check(self._lib.mhte_step_dedup(self._h, vp(ids), C.c_int64(ids.numel()), vp(uids),
+    check(self._lib.mhte_step_dedup(self._h, vp(ids), ids.numel(), vp(uids),
                                     vp(n_unique_dev), _stream()))
 
   def unique_unordered(self, ids: torch.Tensor, want_host_count: bool = False,
@@ -102,20 +102,19 @@ class DedupWorkspace:
     else:
       uids, inverse, lst_start, seg_pos, nu = out[:5]
       lst_end = out.list_end
-    host = C.c_int64(0)
-    check(self._lib.mhte_unique_unordered(self._h, vp(ids), C.c_int64(n), vp(uids), vp(inverse),
+    host = (C.c_int64 * 1)()
+    check(self._lib.mhte_unique_unordered(self._h, vp(ids), n, vp(uids), vp(inverse),
                                           vp(lst_start), vp(lst_end), vp(seg_pos), vp(nu),
-                                          C.byref(host) if want_host_count else None, _stream()))
+                                          host if want_host_count else None, _stream()))
     return UniqueResult(uids, inverse, lst_start, seg_pos, nu,
-                        int(host.value) if want_host_count else None, lst_end)
+                        host[0] if want_host_count else None, lst_end)
 
   def gather_rows(self, src: torch.Tensor, index: torch.Tensor, n: int, dim: int,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[p] = src[index[p]] — FillWithOffsetMap in gather form (unique_mapping_ops.cc:225-242)."""
     if out is None:
       out = torch.empty((n, dim), dtype=torch.float32, device=src.device)
-    check(self._lib.mhte_gather_rows(vp(src), vp(index), C.c_int64(n), C.c_int32(dim), vp(out),
-                                     _stream()))
+    check(self._lib.mhte_gather_rows(vp(src), vp(index), n, dim, vp(out), _stream()))
     return out
 
   def segment_sum(self, grads: torch.Tensor, u: UniqueResult, dim: int,
@@ -126,9 +125,8 @@ class DedupWorkspace:
     if out is None:
       out = torch.zeros((max(n, 1), dim), dtype=torch.float32, device=grads.device)
     check(self._lib.mhte_segment_sum(self._h, vp(grads), vp(u.inverse), vp(u.seg_off),
-                                     vp(u.seg_pos), vp(u.n_unique_dev), C.c_int64(n),
-                                     C.c_int32(dim), vp(out), C.c_int32(1 if exact_order else 0),
-                                     _stream()))
+                                     vp(u.seg_pos), vp(u.n_unique_dev), n, dim, vp(out),
+                                     exact_order, _stream()))
     return out
 
 
@@ -178,8 +176,8 @@ def unique_key_with_value_and_offset(key: Ragged, dims: List[int], generate_buff
     if hi > lo:
       vos = torch.empty(hi - lo + 1, dtype=torch.int64, device=dev)
       check(L.mhte_value_offsets(vp(r.seg_off), vp(r.seg_pos), vp(r.n_unique_dev),
-                                 C.c_int64(hi - lo), C.c_int64(value_base), C.c_int64(dims[t]),
-                                 C.c_int64(lo), vp(value_offset[lo:hi]), vp(vos), _stream()))
+                                 hi - lo, value_base, dims[t], lo, vp(value_offset[lo:hi]), vp(vos),
+                                 _stream()))
       # the reference emits cumulative list ends after a leading 0
       vo_split_parts.append(vos[1:U + 1])
     splits.append(splits[-1] + U)
@@ -217,10 +215,10 @@ def fill_with_offset_map(pos: Ragged, value: torch.Tensor, value_offset_map: tor
   for t in range(T):
     lo, hi = int(pos.row_splits[t]), int(pos.row_splits[t + 1])
     if hi > lo:
-      check(L.mhte_fill_with_offset_map(vp(pos.values[lo:hi]), C.c_int64(hi - lo),
+      check(L.mhte_fill_with_offset_map(vp(pos.values[lo:hi]), hi - lo,
                                         vp(value[voff:]), vp(value_offset_map),
-                                        vp(value_offset_map_split), C.c_int32(dims[t]),
-                                        C.c_int32(vec), vp(value_buffer), _stream()))
+                                        vp(value_offset_map_split), dims[t], vec,
+                                        vp(value_buffer), _stream()))
     voff += (hi - lo) * dims[t]
   return value_buffer
 
@@ -238,10 +236,10 @@ def fill_with_offset_map_gradient(pos: Ragged, grad: torch.Tensor, grad_offset_m
   for t in range(T):
     lo, hi = int(pos.row_splits[t]), int(pos.row_splits[t + 1])
     if hi > lo:
-      check(L.mhte_fill_with_offset_map_gradient(vp(pos.values[lo:hi]), C.c_int64(hi - lo),
+      check(L.mhte_fill_with_offset_map_gradient(vp(pos.values[lo:hi]), hi - lo,
                                                  vp(grad), vp(grad_offset_map),
-                                                 vp(grad_offset_map_split), C.c_int32(dims[t]),
-                                                 C.c_int32(vec), vp(out[ooff:]), _stream()))
+                                                 vp(grad_offset_map_split), dims[t], vec,
+                                                 vp(out[ooff:]), _stream()))
     ooff += (hi - lo) * dims[t]
   return out
 
@@ -267,7 +265,7 @@ def fused_gather_embeddings_by_input(fused_embeddings: torch.Tensor,
   n = (C.c_int64 * len(offs))(*[o.numel() for o in offs])
   dims = (C.c_int32 * len(offs))(*[int(d) for d in embedding_dims])
   check(_lib.lib().mhte_fused_gather_embeddings_by_input(vp(fused_embeddings.contiguous()),
-                                                         C.c_int32(len(offs)), _ptr_array(offs), n,
+                                                         len(offs), _ptr_array(offs), n,
                                                          dims, _ptr_array(outs), _stream()))
   return outs
 
@@ -283,8 +281,8 @@ def fused_gather_embeddings_by_input_gradient(fused_embeddings_size: int, grads:
   n = (C.c_int64 * len(offs))(*[o.numel() for o in offs])
   dims = (C.c_int32 * len(offs))(*[int(d) for d in embedding_dims])
   check(_lib.lib().mhte_fused_gather_embeddings_by_input_gradient(
-      vp(out), C.c_int64(out.numel()), C.c_int32(len(offs)), _ptr_array(gs), _ptr_array(offs), n,
-      dims, C.c_float(float(scale)), _stream()))
+      vp(out), out.numel(), len(offs), _ptr_array(gs), _ptr_array(offs), n,
+      dims, scale, _stream()))
   return out
 
 
@@ -294,9 +292,8 @@ def _reduce(id_indices, id_values, id_length, mode, indices_sorted):
   assert vals.is_cuda and idx.is_cuda and vals.dim() == 2 and idx.numel() == vals.shape[0]
   batch = int(id_length[0]) if not isinstance(id_length, int) else id_length
   out = torch.empty((batch, vals.shape[1]), dtype=torch.float32, device=vals.device)
-  check(_lib.lib().mhte_reduce_rows(vp(idx), vp(vals), C.c_int64(idx.numel()),
-                                    C.c_int32(vals.shape[1]), C.c_int64(batch), C.c_int32(mode),
-                                    C.c_int32(1 if indices_sorted else 0), vp(out), _stream()))
+  check(_lib.lib().mhte_reduce_rows(vp(idx), vp(vals), idx.numel(), vals.shape[1], batch, mode,
+                                    indices_sorted, vp(out), _stream()))
   return out
 
 
@@ -371,8 +368,8 @@ def fused_reduce_and_split_gpu(splits: List[torch.Tensor], embeddings: List[torc
   batch = max(int(splits[0].shape[0]) - 1, 0) if splits else 0
   outs = _aligned_slices(batch, flat, dev)
   check(_lib.lib().mhte_fused_reduce_and_split(
-      vp(fused_splits), rss, _ptr_array(embs), rows, dims, C.c_int32(len(embs)), sdims,
-      C.c_int32(len(flat)), _ptr_array(outs), _stream()))
+      vp(fused_splits), rss, _ptr_array(embs), rows, dims, len(embs), sdims, len(flat),
+      _ptr_array(outs), _stream()))
   return outs
 
 
@@ -398,7 +395,7 @@ def fused_reduce_and_split_gpu_grad(splits: List[torch.Tensor], embeddings: List
   grads = [torch.empty((int(e.shape[0]), int(e.shape[1])), dtype=torch.float32, device=dev)
            for e in embeddings]
   check(_lib.lib().mhte_fused_reduce_and_split_grad(
-      vp(fused_splits), rss, rows, dims, C.c_int32(len(grads)), sdims, C.c_int32(len(flat)),
+      vp(fused_splits), rss, rows, dims, len(grads), sdims, len(flat),
       _ptr_array(gs), _ptr_array(grads), _stream()))
   return grads
 
@@ -549,10 +546,9 @@ def fused_embedding_to_layout(embeddings_list: List[torch.Tensor], fid_offset: t
   outs = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
   lens = (C.c_int64 * len(outs))(*[o.numel() for o in outs])
   check(_lib.lib().mhte_embedding_to_layout(
-      _ptr_array(embs), stride, count, C.c_int32(len(embs)), vp(fo), C.c_int64(fo.numel()), vp(fe),
-      C.c_int64(fe.numel()), vp(nf), C.c_int32(nf.numel()), C.c_int32(int(batch_size)), slices,
-      C.c_int32(len(slices)), _ptr_array(outs), lens, C.c_int32(len(outs)),
-      C.c_int32(_lib.MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS if one_fid_unique_rows else 0), _stream()))
+      _ptr_array(embs), stride, count, len(embs), vp(fo), fo.numel(), vp(fe), fe.numel(), vp(nf),
+      nf.numel(), int(batch_size), slices, len(slices), _ptr_array(outs), lens, len(outs),
+      _lib.MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS if one_fid_unique_rows else 0, _stream()))
   return outs
 
 
@@ -571,10 +567,9 @@ def fused_embedding_to_layout_grad(embeddings_list: List[torch.Tensor], fid_offs
   grads = out if out is not None else [torch.empty_like(e) for e in embs]
   lens = (C.c_int64 * len(tg))(*[g.numel() for g in tg])
   check(_lib.lib().mhte_embedding_to_layout_grad(
-      _ptr_array(grads), stride, count, C.c_int32(len(embs)), vp(fo), C.c_int64(fo.numel()), vp(fe),
-      C.c_int64(fe.numel()), vp(nf), C.c_int32(nf.numel()), C.c_int32(int(batch_size)), slices,
-      C.c_int32(len(slices)), _ptr_array(tg), lens, C.c_int32(len(tg)),
-      C.c_int32(_lib.MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS if one_fid_unique_rows else 0), _stream()))
+      _ptr_array(grads), stride, count, len(embs), vp(fo), fo.numel(), vp(fe), fe.numel(), vp(nf),
+      nf.numel(), int(batch_size), slices, len(slices), _ptr_array(tg), lens, len(tg),
+      _lib.MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS if one_fid_unique_rows else 0, _stream()))
   return grads
 
 
@@ -597,7 +592,7 @@ def lookup_gradient(id_indices: torch.Tensor, id_values: torch.Tensor,
   out_ids = torch.empty(n, dtype=torch.int64, device=dev)
   out = torch.empty((n, dim), dtype=torch.float32, device=dev)
   _lib.check(_lib.lib().mhte_lookup_gradient(
-      _lib.vp(idx), _lib.C.c_int64(n), _lib.C.c_int64(int(idx.shape[1])), _lib.vp(val), _lib.vp(g),
-      _lib.C.c_int64(int(g.shape[0])), _lib.C.c_int32(dim), _lib.vp(out_ids), _lib.vp(out),
+      _lib.vp(idx), n, idx.shape[1], _lib.vp(val), _lib.vp(g), g.shape[0], dim, _lib.vp(out_ids),
+      _lib.vp(out),
       _lib.C.c_void_p(torch.cuda.current_stream().cuda_stream)))
   return out_ids, out

@@ -274,7 +274,7 @@ class SparseStep:
     nu = (C.c_void_p * 3)(*[u.data_ptr() for u in self._nu])
     gp = (C.c_void_p * len(grad_pool))(*[g.data_ptr() for g in grad_pool])
     lrs = np.ascontiguousarray(self.lrs, dtype=np.float32)
-    r = E.mhte_eager_step_loop(
+    r = E.mhte_eager_step_loop(   # (the helper library is not in the header: untyped, so scalars stay wrapped)
         self.table.handle, C.c_int32(self.idx), ws, uid, nu, C.c_int32(at), _lib.vp(ids_all),
         C.c_int64(self.batch), C.c_int64(lo), C.c_int64(hi), _lib.vp(self.emb), gp,
         C.c_int32(len(grad_pool)), _lib.vp(self.grad_u), lrs.ctypes.data_as(C.POINTER(C.c_float)),
@@ -326,8 +326,7 @@ class MultiSparseStep:
     self._lib = table._lib  # pylint: disable=protected-access
     self._dims = table.get_table_dim_sizes()
     h = _lib.C.c_void_p()
-    _lib.check(self._lib.mhte_multi_step_create(table.handle, _lib.C.c_int64(self.batch),
-                                                _lib.C.byref(h)))
+    _lib.check(self._lib.mhte_multi_step_create(table.handle, self.batch, _lib.C.byref(h)))
     self._h = h
     self._ahead = None   # (values tensor, its _version, row_splits bytes) deduplicated ahead
     self._keep = None    # arguments of the launches in flight
@@ -369,9 +368,8 @@ class MultiSparseStep:
       nsp = None
       nv, nsp_p, nsp_n = C.c_void_p(0), None, 0
     _lib.check(self._lib.mhte_multi_step_forward(
-        self._h, _lib.vp(ragged.values), sp.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(sp.size),
-        _lib.vp(out), C.c_int64(out.numel()), nv, nsp_p, C.c_int64(nsp_n),
-        C.c_int32(1 if pre else 0), self._stream()))
+        self._h, _lib.vp(ragged.values), sp.ctypes.data_as(C.POINTER(C.c_int64)), sp.size,
+        _lib.vp(out), out.numel(), nv, nsp_p, nsp_n, pre, self._stream()))
     self._ahead = self._key(next_ragged) if next_ragged is not None else None
     self._keep = (ragged, next_ragged, out)
     return out
@@ -380,10 +378,9 @@ class MultiSparseStep:
     C = _lib.C
     lrs = np.ascontiguousarray(self.table.learning_rate, dtype=np.float32)
     _lib.check(self._lib.mhte_multi_step_backward(
-        self._h, _lib.vp(flat_grad), C.c_int64(flat_grad.numel()),
-        lrs.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(lrs.size), C.c_int64(int(update_time)),
-        C.c_int64(int(global_step)), C.c_int32(_lib.MHTE_EXACT_ORDER if self.exact_order else 0),
-        self._stream()))
+        self._h, _lib.vp(flat_grad), flat_grad.numel(), lrs.ctypes.data_as(C.POINTER(C.c_float)),
+        lrs.size, int(update_time), int(global_step),
+        _lib.MHTE_EXACT_ORDER if self.exact_order else 0, self._stream()))
 
   def unique_counts(self) -> np.ndarray:
     """Distinct ids per table of the batch last given to ``forward`` (synchronises)."""

@@ -104,25 +104,23 @@ class HashFilter:
     self._device = torch.cuda.current_device() if device is None else int(device)
     h = C.c_void_p()
     if config is None:
-      check(self._lib.mhte_hash_filter_create(C.c_uint64(int(capacity)), C.c_int32(int(split_num)),
-                                              C.c_int32(self._device), C.byref(h)))
+      check(self._lib.mhte_hash_filter_create(int(capacity), int(split_num), self._device,
+                                              C.byref(h)))
     else:
       check(self._lib.mhte_hash_filter_create_from_proto(
-          C.c_uint64(int(capacity)), C.c_int32(int(split_num)), config, C.c_int64(len(config)),
-          C.c_int32(self._device), C.byref(h)))
+          int(capacity), int(split_num), config, len(config), self._device, C.byref(h)))
     self._h = h
 
   def get(self, ids: torch.Tensor) -> torch.Tensor:
     """Seen counts (0..15) of ``ids`` (Filter::get)."""
     ids = ids.to(device="cuda:%d" % self._device, dtype=torch.int64).contiguous()
     out = torch.empty(ids.numel(), dtype=torch.int32, device=ids.device)
-    check(self._lib.mhte_hash_filter_get(self._h, vp(ids), C.c_int64(ids.numel()), vp(out),
-                                         _stream()))
+    check(self._lib.mhte_hash_filter_get(self._h, vp(ids), ids.numel(), vp(out), _stream()))
     return out
 
   def _stats(self):
     out = (C.c_int64 * (4 + 64))()
-    check(self._lib.mhte_hash_filter_stats(self._h, out, C.c_int32(4 + 64), _stream()))
+    check(self._lib.mhte_hash_filter_stats(self._h, out, 4 + 64, _stream()))
     return out
 
   def num_elements(self) -> List[int]:
@@ -175,8 +173,7 @@ class ProbabilisticFilter(HashFilter):
     self._device = torch.cuda.current_device() if device is None else int(device)
     h = C.c_void_p()
     check(self._lib.mhte_hash_filter_create_probabilistic(
-        C.c_int32(1 if equal_probability else 0), C.c_uint64(int(seed)), config,
-        C.c_int64(len(config) if config else 0), C.c_int32(self._device), C.byref(h)))
+        equal_probability, int(seed), config, len(config) if config else 0, self._device, C.byref(h)))
     self._h = h
 
 
@@ -282,17 +279,16 @@ class MultiHashTable:
     ragged_id = self.get_ragged_id({k: v[0] for k, v in slot_to_id_and_value.items()})
     flat_value = self.get_flat_value({k: v[1] for k, v in slot_to_id_and_value.items()})
     check(self._lib.mhte_assign_add(self._h, vp(ragged_id.values), _i64p(ragged_id.row_splits),
-                                    C.c_int64(ragged_id.row_splits.size), vp(flat_value),
-                                    C.c_int64(flat_value.numel()), C.c_int64(int(req_time)),
-                                    C.c_int32(0), _stream()))
+                                    ragged_id.row_splits.size, vp(flat_value), flat_value.numel(),
+                                    int(req_time), 0, _stream()))
     return self
 
   def reinitialize(self, slot: str, ids: torch.Tensor,
                    now: int = 0) -> Tuple["MultiHashTable", torch.Tensor]:
     ids = self._dev(ids, torch.int64)
     status = torch.empty(ids.numel(), dtype=torch.int32, device=ids.device)
-    check(self._lib.mhte_reinitialize(self._h, slot.encode(), vp(ids), C.c_int64(ids.numel()),
-                                      vp(status), C.c_int64(int(now)), _stream()))
+    check(self._lib.mhte_reinitialize(self._h, slot.encode(), vp(ids), ids.numel(),
+                                      vp(status), int(now), _stream()))
     return self, status
 
   def lookup(self, slot_to_id: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -322,15 +318,15 @@ class MultiHashTable:
     splits = np.empty(num_of_shards, np.int32)
     id_off = np.empty(T * num_of_shards + 1, np.int32)
     emb_off = np.empty(T * num_of_shards + 1, np.int32)
-    tk, te = C.c_int64(0), C.c_int64(0)
-    check(self._lib.mhte_compute_fused_offsets(self._h, _i32p(fss), C.c_int32(num_of_shards),
+    tk, te = (C.c_int64 * 1)(), (C.c_int64 * 1)()
+    check(self._lib.mhte_compute_fused_offsets(self._h, _i32p(fss), num_of_shards,
                                                _i32p(id_off), _i32p(emb_off), _i32p(splits),
-                                               C.byref(tk), C.byref(te)))
-    if tk.value > ids.numel():
+                                               tk, te))
+    if tk[0] > ids.numel():
       raise _lib.InvalidArgumentError(_lib.MHTE_INVALID_ARGUMENT, "ids shorter than fused_slot_size")
-    emb = torch.empty(te.value, dtype=torch.float32, device=ids.device)
-    check(self._lib.mhte_fused_lookup(self._h, vp(ids), _i32p(fss), C.c_int32(num_of_shards),
-                                      C.c_int64(int(req_time)), vp(emb), C.c_int64(emb.numel()),
+    emb = torch.empty(te[0], dtype=torch.float32, device=ids.device)
+    check(self._lib.mhte_fused_lookup(self._h, vp(ids), _i32p(fss), num_of_shards,
+                                      int(req_time), vp(emb), emb.numel(),
                                       _i32p(splits), _i32p(id_off), _i32p(emb_off), _stream()))
     return emb, splits, id_off, emb_off, ids
 
@@ -348,11 +344,10 @@ class MultiHashTable:
     flags = (_lib.MHTE_SUM_DUPLICATES if enable_grad_accumulation else 0) | (
         _lib.MHTE_IDS_UNIQUE if ids_unique_per_segment else 0)
     check(self._lib.mhte_fused_optimize(self._h, vp(ids), _i32p(fss), vp(id_grads),
-                                        C.c_int64(id_grads.numel()), _i32p(ko), _i32p(go),
+                                        id_grads.numel(), _i32p(ko), _i32p(go),
                                         _f32p(self._learning_rate),
-                                        C.c_int64(self._learning_rate.size),
-                                        C.c_int64(int(req_time)), C.c_int64(int(global_step)),
-                                        C.c_int32(num_of_shards), C.c_int32(flags), _stream()))
+                                        self._learning_rate.size, int(req_time), int(global_step),
+                                        num_of_shards, flags, _stream()))
     return self
 
   # ------------------------------------------------------------------ RawMultiTypeHashTable
@@ -362,8 +357,7 @@ class MultiHashTable:
         self._dims) else 0
     out = torch.empty(total, dtype=torch.float32, device=ragged_id.values.device)
     check(self._lib.mhte_lookup(self._h, vp(ragged_id.values), _i64p(ragged_id.row_splits),
-                                C.c_int64(ragged_id.row_splits.size), vp(out),
-                                C.c_int64(out.numel()), _stream()))
+                                ragged_id.row_splits.size, vp(out), out.numel(), _stream()))
     return out
 
   def maybe_evict(self, force_check: bool = False) -> List[str]:
@@ -384,20 +378,18 @@ class MultiHashTable:
                           req_time: int = 0, ids_unique: bool = False) -> "MultiHashTable":
     flat_grad = self._dev(flat_grad, torch.float32)
     check(self._lib.mhte_optimize(self._h, vp(ragged_id.values), _i64p(ragged_id.row_splits),
-                                  C.c_int64(ragged_id.row_splits.size), vp(flat_grad),
-                                  C.c_int64(flat_grad.numel()), _f32p(self._learning_rate),
-                                  C.c_int64(self._learning_rate.size), C.c_int64(int(req_time)),
-                                  C.c_int64(int(global_step)),
-                                  C.c_int32(_lib.MHTE_IDS_UNIQUE if ids_unique else 0), _stream()))
+                                  ragged_id.row_splits.size, vp(flat_grad),
+                                  flat_grad.numel(), _f32p(self._learning_rate),
+                                  self._learning_rate.size, int(req_time), int(global_step),
+                                  _lib.MHTE_IDS_UNIQUE if ids_unique else 0, _stream()))
     return self
 
   def raw_assign(self, ragged_id: Ragged, flat_value: torch.Tensor,
                  req_time: int = 0) -> "MultiHashTable":
     flat_value = self._dev(flat_value, torch.float32)
     check(self._lib.mhte_assign(self._h, vp(ragged_id.values), _i64p(ragged_id.row_splits),
-                                C.c_int64(ragged_id.row_splits.size), vp(flat_value),
-                                C.c_int64(flat_value.numel()), C.c_int64(int(req_time)),
-                                C.c_int32(0), _stream()))
+                                ragged_id.row_splits.size, vp(flat_value), flat_value.numel(),
+                                int(req_time), 0, _stream()))
     return self
 
   def get_embeddings(self, ragged_id: Ragged, value: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -447,9 +439,9 @@ class MultiHashTable:
     lrs = np.zeros(1 << 16, dtype=np.float32)   # (one float per segment of the model; checked below)
     h = C.c_void_p()
     check(self._lib.mhte_multi_table_create_from_proto(
-        config, C.c_int64(len(config)), hash_filter._h if hash_filter is not None else C.c_void_p(0),  # pylint: disable=protected-access
-        C.c_uint64(int(reserve_rows)), C.c_float(float(max_load_factor)), C.c_int32(self._device),
-        self._shared_name.encode(), _f32p(lrs), C.c_int32(lrs.size), C.byref(h)))
+        config, len(config), hash_filter._h if hash_filter is not None else C.c_void_p(0),  # pylint: disable=protected-access
+        int(reserve_rows), max_load_factor, self._device, self._shared_name.encode(), _f32p(lrs),
+        lrs.size, C.byref(h)))
     self._h = h
     self._hash_filter = hash_filter
     MultiHashTable._names_in_use.add(self._shared_name)
@@ -478,15 +470,15 @@ class MultiHashTable:
     ragged_id = self.get_ragged_id(slot_to_id)
     n = int(ragged_id.row_splits[-1])
     offs = np.zeros(n + 1, dtype=np.int64)
-    need = C.c_int64(0)
+    need = (C.c_int64 * 1)()
     cap = max(1, n) * 64
     while True:
       buf = C.create_string_buffer(cap)
       rc = self._lib.mhte_lookup_entry(self._h, vp(ragged_id.values), _i64p(ragged_id.row_splits),
-                                       C.c_int64(ragged_id.row_splits.size), buf, C.c_int64(cap),
-                                       _i64p(offs), C.byref(need), _stream())
-      if rc == _lib.MHTE_INVALID_ARGUMENT and need.value > cap:
-        cap = int(need.value)
+                                       ragged_id.row_splits.size, buf, cap,
+                                       _i64p(offs), need, _stream())
+      if rc == _lib.MHTE_INVALID_ARGUMENT and need[0] > cap:
+        cap = need[0]
         continue
       check(rc)
       break
@@ -530,21 +522,20 @@ class MultiHashTable:
     i = name_or_idx if isinstance(name_or_idx, int) else self._index(name_or_idx)
     n_off = max(int(limit), 1) + 1
     offs = np.zeros(n_off, dtype=np.int64)
-    new_offset, n_ent, need = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    new_offset, n_ent, need = (C.c_int64 * 1)(), (C.c_int64 * 1)(), (C.c_int64 * 1)()
     cap = max(1, int(limit)) * 64
     while True:
       buf = C.create_string_buffer(cap)
       rc = self._lib.mhte_table_save_as_tensor(
-          self._h, C.c_int32(i), C.c_int32(int(shard_idx)), C.c_int32(int(num_shards)), C.c_int64(int(limit)),
-          C.c_int64(int(offset)), C.byref(new_offset), buf, C.c_int64(cap), _i64p(offs), C.c_int64(n_off),
-          C.byref(n_ent), C.byref(need), _stream())
-      if rc == _lib.MHTE_INVALID_ARGUMENT and need.value > cap:
-        cap = int(need.value)
+          self._h, i, int(shard_idx), int(num_shards), int(limit), int(offset), new_offset, buf, cap,
+          _i64p(offs), n_off, n_ent, need, _stream())
+      if rc == _lib.MHTE_INVALID_ARGUMENT and need[0] > cap:
+        cap = need[0]
         continue
       check(rc)
       break
     raw = buf.raw
-    return int(new_offset.value), [raw[offs[k]:offs[k + 1]] for k in range(int(n_ent.value))]
+    return new_offset[0], [raw[offs[k]:offs[k + 1]] for k in range(n_ent[0])]
 
   @staticmethod
   def feature_stat(basename: str) -> Dict[str, int]:
@@ -552,10 +543,9 @@ class MultiHashTable:
     L = _lib.lib()
     names = C.create_string_buffer(1 << 16)
     counts = (C.c_uint64 * 1024)()
-    n = C.c_int32(0)
-    check(L.mhte_feature_stat(basename.encode("utf-8"), names, C.c_int64(len(names)), counts,
-                              C.c_int32(1024), C.byref(n)))
-    parts = names.raw.split(b"\0")[:n.value]
+    n = (C.c_int32 * 1)()
+    check(L.mhte_feature_stat(basename.encode("utf-8"), names, len(names), counts, 1024, n))
+    parts = names.raw.split(b"\0")[:n[0]]
     return {p.decode(): int(counts[i]) for i, p in enumerate(parts)}
 
   # ------------------------------------------------------------------ introspection / maintenance
@@ -566,26 +556,24 @@ class MultiHashTable:
     return i
 
   def size(self, name: str) -> int:
-    n = C.c_int64(0)
-    check(self._lib.mhte_table_size(self._h, C.c_int32(self._index(name)), C.byref(n), _stream()))
-    return int(n.value)
+    n = (C.c_int64 * 1)()
+    check(self._lib.mhte_table_size(self._h, self._index(name), n, _stream()))
+    return n[0]
 
   def stats(self, name: str) -> _lib.TableStats:
     s = _lib.TableStats()
-    check(self._lib.mhte_table_get_stats(self._h, C.c_int32(self._index(name)), C.byref(s),
-                                         _stream()))
+    check(self._lib.mhte_table_get_stats(self._h, self._index(name), C.byref(s), _stream()))
     return s
 
   def set_count_hits(self, name: str, enable: bool = True) -> "MultiHashTable":
-    check(self._lib.mhte_table_set_count_hits(self._h, C.c_int32(self._index(name)),
-                                              C.c_int32(1 if enable else 0)))
+    check(self._lib.mhte_table_set_count_hits(self._h, self._index(name), enable))
     return self
 
   def contains(self, name: str, ids: torch.Tensor) -> torch.Tensor:
     ids = self._dev(ids, torch.int64)
     out = torch.empty(ids.numel(), dtype=torch.int32, device=ids.device)
-    check(self._lib.mhte_table_contains(self._h, C.c_int32(self._index(name)), vp(ids),
-                                        C.c_int64(ids.numel()), vp(out), _stream()))
+    check(self._lib.mhte_table_contains(self._h, self._index(name), vp(ids), ids.numel(),
+                                        vp(out), _stream()))
     return out.bool()
 
   def save(self, basename: str, nshards: int = -1) -> "MultiHashTable":
@@ -596,8 +584,7 @@ class MultiHashTable:
     d = os.path.dirname(basename)
     if d:
       os.makedirs(d, exist_ok=True)
-    check(self._lib.mhte_multi_table_save(self._h, basename.encode("utf-8"), C.c_int32(int(nshards)),
-                                          _stream()))
+    check(self._lib.mhte_multi_table_save(self._h, basename.encode("utf-8"), int(nshards), _stream()))
     return self
 
   def restore(self, basename: str) -> "MultiHashTable":
@@ -615,25 +602,23 @@ class MultiHashTable:
     d = os.path.dirname(basename)
     if d:
       os.makedirs(d, exist_ok=True)
-    check(self._lib.mhte_table_save(self._h, C.c_int32(self._index(name)), basename.encode("utf-8"),
-                                    C.c_int32(int(nshards)), _stream()))
+    check(self._lib.mhte_table_save(self._h, self._index(name), basename.encode("utf-8"),
+                                    int(nshards), _stream()))
     return self
 
   def restore_table(self, name: str, basename: str) -> "MultiHashTable":
     """HashTable.restore of ONE table (NT/hash_table_ops.py:322-325, MonolithHashTableRestore):
     validates the shard set, CLEARS the table, then upserts every record of every shard."""
-    check(self._lib.mhte_table_restore(self._h, C.c_int32(self._index(name)), basename.encode("utf-8"),
-                                       _stream()))
+    check(self._lib.mhte_table_restore(self._h, self._index(name), basename.encode("utf-8"), _stream()))
     return self
 
   def clear_table(self, name: str) -> "MultiHashTable":
     """EmbeddingHashTableInterface::Clear: no entries, capacity kept."""
-    check(self._lib.mhte_table_clear(self._h, C.c_int32(self._index(name)), _stream()))
+    check(self._lib.mhte_table_clear(self._h, self._index(name), _stream()))
     return self
 
   def evict(self, name: str, max_update_time: int = -1) -> "MultiHashTable":
-    check(self._lib.mhte_table_evict(self._h, C.c_int32(self._index(name)),
-                                     C.c_int64(int(max_update_time)), _stream()))
+    check(self._lib.mhte_table_evict(self._h, self._index(name), int(max_update_time), _stream()))
     return self
 
   def dump(self, name: str, with_rows: bool = True):
@@ -646,18 +631,16 @@ class MultiHashTable:
     pos = torch.empty(n + 1, dtype=torch.int64, device=dev)
     ts = torch.empty(n + 1, dtype=torch.int32, device=dev)
     rows = torch.empty((n + 1, rf), dtype=torch.float32, device=dev) if with_rows else None
-    m = C.c_int64(0)
-    check(self._lib.mhte_table_dump(self._h, C.c_int32(i), C.c_int64(n + 1), vp(ids), vp(pos),
-                                    vp(ts), vp(rows), C.byref(m), _stream()))
-    m = int(m.value)
+    m = (C.c_int64 * 1)()
+    check(self._lib.mhte_table_dump(self._h, i, n + 1, vp(ids), vp(pos), vp(ts), vp(rows), m, _stream()))
+    m = m[0]
     return ids[:m], pos[:m], ts[:m], (rows[:m] if with_rows else None)
 
   # single-table, device-side-count forms used by the fused step and the bench
   def table_lookup_n(self, name_or_idx, ids: torch.Tensor, n_dev: Optional[torch.Tensor],
                      out: torch.Tensor, n_max: Optional[int] = None):
     i = name_or_idx if isinstance(name_or_idx, int) else self._index(name_or_idx)
-    check(self._lib.mhte_table_lookup_n(self._h, C.c_int32(i), vp(ids),
-                                        C.c_int64(ids.numel() if n_max is None else n_max),
+    check(self._lib.mhte_table_lookup_n(self._h, i, vp(ids), ids.numel() if n_max is None else n_max,
                                         vp(n_dev), vp(out), _stream()))
     return out
 
@@ -666,11 +649,9 @@ class MultiHashTable:
                        flags: int = _lib.MHTE_IDS_UNIQUE, n_max: Optional[int] = None):
     i = name_or_idx if isinstance(name_or_idx, int) else self._index(name_or_idx)
     lrs = np.ascontiguousarray(lrs, dtype=np.float32)
-    check(self._lib.mhte_table_optimize_n(self._h, C.c_int32(i), vp(ids),
-                                          C.c_int64(ids.numel() if n_max is None else n_max),
-                                          vp(n_dev), vp(grads), _f32p(lrs), C.c_int64(lrs.size),
-                                          C.c_int64(int(update_time)), C.c_int64(int(global_step)),
-                                          C.c_int32(flags), _stream()))
+    check(self._lib.mhte_table_optimize_n(self._h, i, vp(ids), ids.numel() if n_max is None else n_max,
+                                          vp(n_dev), vp(grads), _f32p(lrs), lrs.size,
+                                          int(update_time), int(global_step), flags, _stream()))
     return self
 
   def table_sum_optimize_n(self, name_or_idx, ws, u, grads: torch.Tensor, grad_unique: torch.Tensor,
@@ -685,17 +666,16 @@ class MultiHashTable:
     n = u.inverse.numel() if n_max is None else n_max
     list_end = u.list_end if u.list_end is not None else u.seg_off[1:]
     check(self._lib.mhte_table_sum_optimize_n(
-        self._h, C.c_int32(i), ws._h, vp(u.unique_ids), C.c_int64(n), vp(u.n_unique_dev),  # pylint: disable=protected-access
-        vp(grads), vp(u.inverse), vp(u.seg_off), vp(list_end), vp(u.seg_pos), C.c_int64(n),
-        vp(grad_unique),
-        _f32p(lrs), C.c_int64(lrs.size), C.c_int64(int(update_time)), C.c_int64(int(global_step)),
-        C.c_int32((_lib.MHTE_EXACT_ORDER if exact_order else 0) |
-                  (_lib.MHTE_DEFER_SLOWPATH if defer_slowpath else 0)), _stream()))
+        self._h, i, ws._h, vp(u.unique_ids), n, vp(u.n_unique_dev),  # pylint: disable=protected-access
+        vp(grads), vp(u.inverse), vp(u.seg_off), vp(list_end), vp(u.seg_pos), n,
+        vp(grad_unique), _f32p(lrs), lrs.size, int(update_time), int(global_step),
+        (_lib.MHTE_EXACT_ORDER if exact_order else 0) |
+        (_lib.MHTE_DEFER_SLOWPATH if defer_slowpath else 0), _stream()))
     return self
 
   def table_finish_pending(self, name_or_idx):
     i = name_or_idx if isinstance(name_or_idx, int) else self._index(name_or_idx)
-    check(self._lib.mhte_table_finish_pending(self._h, C.c_int32(i), _stream()))
+    check(self._lib.mhte_table_finish_pending(self._h, i, _stream()))
     return self
 
   # pipelined step: the dedup of the next batch rides in the two launches of the current one
@@ -709,9 +689,9 @@ class MultiHashTable:
     update will need."""
     i = name_or_idx if isinstance(name_or_idx, int) else self._index(name_or_idx)
     check(self._lib.mhte_table_step_forward(
-        self._h, C.c_int32(i), vp(ids), C.c_int64(ids.numel()), vp(out),
+        self._h, i, vp(ids), ids.numel(), vp(out),
         ws_next._h if ws_next is not None else C.c_void_p(0),  # pylint: disable=protected-access
-        vp(next_ids), C.c_int64(next_ids.numel() if next_ids is not None else 0), vp(uids_next),
+        vp(next_ids), next_ids.numel() if next_ids is not None else 0, vp(uids_next),
         vp(n_unique_next),
         ws_cur._h if ws_cur is not None else C.c_void_p(0),  # pylint: disable=protected-access
         _stream()))
@@ -731,12 +711,12 @@ class MultiHashTable:
     lrs = np.ascontiguousarray(lrs, dtype=np.float32)
     n = grads.shape[0]
     check(self._lib.mhte_table_step_backward_ahead(
-        self._h, C.c_int32(i), ws._h,  # pylint: disable=protected-access
+        self._h, i, ws._h,  # pylint: disable=protected-access
         ws_next._h if ws_next is not None else C.c_void_p(0),  # pylint: disable=protected-access
-        vp(uids), C.c_int64(uids.numel()), vp(n_unique_dev), vp(grads), C.c_int64(n),
-        vp(grad_unique), _f32p(lrs), C.c_int64(lrs.size), C.c_int64(int(update_time)),
-        C.c_int64(int(global_step)), C.c_int32(_lib.MHTE_EXACT_ORDER if exact_order else 0),
+        vp(uids), uids.numel(), vp(n_unique_dev), vp(grads), n,
+        vp(grad_unique), _f32p(lrs), lrs.size, int(update_time), int(global_step),
+        _lib.MHTE_EXACT_ORDER if exact_order else 0,
         ws_ahead._h if ws_ahead is not None else C.c_void_p(0),  # pylint: disable=protected-access
-        vp(ahead_ids), C.c_int64(ahead_ids.numel() if ahead_ids is not None else 0), vp(uids_ahead),
+        vp(ahead_ids), ahead_ids.numel() if ahead_ids is not None else 0, vp(uids_ahead),
         vp(n_unique_ahead), _stream()))
     return self

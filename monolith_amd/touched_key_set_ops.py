@@ -34,8 +34,7 @@ class TouchedKeySet:
     self._name = "_".join([TouchedKeySet.NAME_PREFIX, name_suffix])
     self._device = (torch.cuda.current_device() if torch.cuda.is_available() else 0) if device is None else int(device)
     h = C.c_void_p()
-    check(self._lib.mhte_touched_key_set_create(C.c_int64(self._capacity), C.c_int64(int(max_insert)),
-                                                C.c_int32(self._device), C.byref(h)))
+    check(self._lib.mhte_touched_key_set_create(self._capacity, int(max_insert), self._device, C.byref(h)))
     self._h = h
 
   @property
@@ -64,8 +63,7 @@ class TouchedKeySet:
     """Enqueues the insert of ``ids`` (of its first ``n_dev[0]`` entries when ``n_dev``, a uint32-sized
     device counter, is given) under ``tag``; nothing comes back to the host."""
     ids = ids.to(device="cuda:%d" % self._device, dtype=torch.int64).contiguous().reshape(-1)
-    check(self._lib.mhte_touched_key_set_insert(self._h, vp(ids), C.c_int64(ids.numel()), vp(n_dev),
-                                                C.c_int32(int(tag)), _stream()))
+    check(self._lib.mhte_touched_key_set_insert(self._h, vp(ids), ids.numel(), vp(n_dev), int(tag), _stream()))
     return self
 
   def insert(self, ids: torch.Tensor) -> int:
@@ -80,9 +78,9 @@ class TouchedKeySet:
     cap = self.stats()[0]
     ids = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
     tags = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    n = C.c_int64(0)
-    check(self._lib.mhte_touched_key_set_steal(self._h, vp(ids), vp(tags), C.c_int64(cap), C.byref(n), _stream()))
-    return ids[:n.value], tags[:n.value]
+    n = (C.c_int64 * 1)()
+    check(self._lib.mhte_touched_key_set_steal(self._h, vp(ids), vp(tags), cap, n, _stream()))
+    return ids[:n[0]], tags[:n[0]]
 
   def steal(self) -> torch.Tensor:
     """touched_key_set_ops.steal: the ids (int64) of the set, which is empty afterwards."""
