@@ -686,7 +686,8 @@ struct Table {
   std::vector<int32_t> expire_days;
   DevBuf<int64_t> d_expire_slots;
   DevBuf<int32_t> d_expire_days;
-  DevBuf<uint32_t> pending;
+  DevBuf<uint32_t> pending;         // displacement list: one word per entry (index into the op's ids); two words
+                                    // in the segment and shard lists (SegUpsertArgs, ShardOwnerArgs)
   DevBuf<uint32_t> skip;            // first admitted occurrence of deferred ids (admission filter)
   // admission: per-feature-slot occurrence thresholds (SlotOccurrenceThresholdConfig) + the filter
   int32_t occ_default = 0;
@@ -1023,6 +1024,12 @@ struct Table {
   }
 
   // ---------------------------------------------------------------- upsert + apply
+  // the displacement pass's instance for a lane width (launch_upsert, finish_pending)
+  template <int OP>
+  static auto slowpath_fn(int vec) {
+    return vec == 4 ? slowpath_kernel<4, OP> : slowpath_kernel<1, OP>;
+  }
+
   template <int OP>
   void launch_upsert(const int64_t* ids, int64_t n, const uint32_t* n_dev, const float* values,
                      const uint32_t* seg_off, const uint32_t* seg_pos, const ApplyArgs& a,
@@ -1050,11 +1057,7 @@ struct Table {
   } while (0)
     DISPATCH_G_VEC(sh, CALL);
 #undef CALL
-    if (sh.VEC == 4) {
-      slowpath_kernel<4, OP><<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
-    } else {
-      slowpath_kernel<1, OP><<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
-    }
+    slowpath_fn<OP>(sh.VEC)<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
     if (a.filter_mode) filter_maintain(st, uint64_t(n));
     HIP_OK(hipGetLastError());
   }
@@ -1454,13 +1457,8 @@ struct Table {
     if (!pend_valid) return;
     pend_valid = false;
     ++mut_epoch;
-    if (pend_vec == 4) {
-      LAUNCH_HOT(kTagSlowpath, (slowpath_kernel<4, kOpOptimize>), 1, 64, st, view, pend_uids,
-                 pend_grad, nullptr, nullptr, pend_args, nullptr, pending.p, nullptr);
-    } else {
-      LAUNCH_HOT(kTagSlowpath, (slowpath_kernel<1, kOpOptimize>), 1, 64, st, view, pend_uids,
-                 pend_grad, nullptr, nullptr, pend_args, nullptr, pending.p, nullptr);
-    }
+    LAUNCH_HOT(kTagSlowpath, slowpath_fn<kOpOptimize>(pend_vec), 1, 64, st, view, pend_uids, pend_grad,
+               nullptr, nullptr, pend_args, nullptr, pending.p, nullptr);
     HIP_OK(hipGetLastError());
   }
 

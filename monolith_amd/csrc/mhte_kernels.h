@@ -1492,9 +1492,101 @@ __device__ __forceinline__ long long wave_insert_slot(Bucket* buckets, uint32_t 
   return -1;
 }
 
-// GATED: other workgroups of the same launch wait for n_pending == 0 before they touch the table
-// (lookup_role's gate): the pass ends with an agent-scope release (its bucket and row stores are
-// written back from this XCD's L2) followed by an agent-scope store of the 0.
+// ---------------------------------------------------------------------------------------------
+// The displacement pass: an id whose two buckets are full went to its table's pending list; one
+// wavefront per table finishes the list later, id by id — slow_place (row handle, slot, timestamp),
+// the update with 64 lanes (apply_row / apply_row_wave), slow_pass_done.  Every update path runs
+// these pieces; where the id, its gradient row and its index come from, and what is applied, is
+// the caller's loop (slowpath_role, seg_slow_kernel, shard_slow_role, shard_slow_all_role).
+// restore_slowpath_kernel and slowpath_par_role order their steps differently and say why.
+// ---------------------------------------------------------------------------------------------
+// (segment kernels) bit 1 of a shape code: the table has a whole-segment optimizer (GroupAdaGrad,
+// group_adagrad_segment) — served by the GROUP instance of seg_upsert_kernel / shard_upsert_kernel
+constexpr uint32_t kShapeGroupBit = 2u;
+
+// a search found no slot (the table is over its load limit), lane 0: the key is not inserted,
+// reported at the next host call ...
+__device__ __forceinline__ void slow_report_drop(const TableView& tv) {
+  atomicOr(&tv.ctr->error, 1u);
+  atomicAdd(&tv.ctr->n_dropped, 1u);
+}
+// ... and the key the pass had counted goes back (the row handle stays stranded)
+__device__ __forceinline__ void slow_give_back(const TableView& tv) {
+  atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));  // - (1 << 32): not a live key
+  slow_report_drop(tv);
+}
+
+// One pending id gets its row handle and its slot, stamped with the update's time a.ts.  Every lane
+// calls it; ok: the id is in the table and r is its row handle, on every lane; !ok: the search
+// found no slot, slow_give_back has run.
+// Who else may touch q, path and the buckets: nobody — lane 0 alone writes them, the other lanes
+// read q and the buckets in the search, and no other wavefront works on the table while a pass
+// runs (a pass runs alone by contract; in a gated launch the lookups wait for slow_pass_done).
+// Between two ids the caller orders lane 0's stores before the wavefront's next loads: a kernel
+// of one wavefront with __syncthreads(); a role beside other wavefronts of its workgroup, or
+// inside another kernel, where a barrier is not its to take, with s_waitcnt vmcnt(0) lgkmcnt(0).
+// The gated single-table role (slowpath_role, SOLO = false) has neither and keeps it so: every
+// wait there is paid by all the workgroups at the gate.
+struct SlowPlaced {
+  uint32_t r;
+  bool ok;
+};
+__device__ __forceinline__ SlowPlaced slow_place(const TableView& tv, int64_t id, const ApplyArgs& a, BfsSlot* q,
+                                                 CuckooRecord* path, int lane) {
+  // the row handle is allocated while the slot search runs (a search that fails gives the key
+  // back and strands the handle)
+  uint32_t r;  // (only lane 0's value is read; merging it with a constant here would make the
+               // compiler wait for the atomic before the search instead of after it)
+  if (lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
+  const long long pos = wave_insert_slot(tv.buckets, tv.hp, id, q, path, lane);
+  if (lane == 0) {
+    if (pos >= 0) {
+      Bucket* b = tv.buckets + (pos >> 2);
+      b->row[pos & 3] = r;
+      b->ts[pos & 3] = a.ts;
+    } else {
+      slow_give_back(tv);
+    }
+  }
+  r = __shfl(r, 0);
+  return SlowPlaced{r, pos >= 0};
+}
+
+// the 64-lane update of a row whose table's shape is known at run time only: bit 0 of the shape
+// code = scalar lanes (VEC 1, else 4), kShapeGroupBit = the GROUP form (rare path: every form in
+// one kernel).  BASIC (SGD / Adagrad / FTRL rows) has no group form.
+template <int OP, bool BASIC>
+__device__ __forceinline__ void apply_row_wave(const TableView& tv, uint32_t shape_code, float* rp, bool is_new,
+                                               int lane, const float* __restrict__ values, int64_t index,
+                                               const ApplyArgs& a) {
+#define MHTE_APPLY_WAVE(V_, GRP_) \
+  apply_row<64, V_, OP, BASIC, GRP_>(tv, rp, is_new, lane, values, nullptr, 0u, 1u, index, a)
+  const bool grp = !BASIC && (shape_code & kShapeGroupBit) != 0u;
+  if (shape_code & 1u) {
+    if (grp) MHTE_APPLY_WAVE(1, true);
+    else MHTE_APPLY_WAVE(1, false);
+  } else {
+    if (grp) MHTE_APPLY_WAVE(4, true);
+    else MHTE_APPLY_WAVE(4, false);
+  }
+#undef MHTE_APPLY_WAVE
+}
+
+// the end of a pass.  GATED: other workgroups of the same launch wait for n_pending == 0 before
+// they touch the table (lookup_role's gate) — an agent-scope release (the pass's bucket and row
+// stores are written back from this XCD's L2) followed by an agent-scope store of the 0.
+template <bool GATED>
+__device__ __forceinline__ void slow_pass_done(const TableView& tv, int lane) {
+  if (GATED) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (lane == 0) __hip_atomic_store(&tv.ctr->n_pending, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    if (lane == 0) tv.ctr->n_pending = 0;
+  }
+}
+
+// The single-table pass: ids[pending[i]] (one word per entry), one entry or the id's occurrence
+// list, or a reinit with its status.  GATED: inside step_fwd_kernel (slow_pass_done).
 // BASIC (gated launches = the fused step kernels): the update code of SGD / Adagrad / FTRL only.
 template <int VEC, int OP, bool SOLO, bool GATED = false, bool BASIC = GATED>
 __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t* __restrict__ ids,
@@ -1513,30 +1605,12 @@ __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t
   if (np == 0) return;
   for (uint32_t i = 0; i < np; ++i) {
     const uint32_t g = i == 0 ? first : pending[i];
-    const int64_t id = ids[g];
-    // the row handle is allocated while the slot search runs (a search that fails — the table is
-    // over its load limit — gives the key back and strands the handle)
-    uint32_t r;  // (only lane 0's value is read; merging it with a constant here would make the
-                 // compiler wait for the atomic before the search instead of after it)
-    if (lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
-    long long pos = wave_insert_slot(tv.buckets, tv.hp, id, q, path, lane);
-    if (lane == 0) {
-      if (pos >= 0) {
-        Bucket* b = tv.buckets + (pos >> 2);
-        b->row[pos & 3] = r;
-        b->ts[pos & 3] = a.ts;
-      } else {
-        atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));  // - (1 << 32): not a live key
-        atomicOr(&tv.ctr->error, 1u);
-        atomicAdd(&tv.ctr->n_dropped, 1u);
-      }
-    }
-    r = __shfl(r, 0);
-    if (pos >= 0) {
+    const SlowPlaced pl = slow_place(tv, ids[g], a, q, path, lane);
+    if (pl.ok) {
       // (skip: first occurrence the admission filter let through, upsert_kernel)
       const uint32_t q0 = (skip && seg_off) ? skip[g] : (seg_off ? seg_off[g] : 0u);
       const uint32_t q1 = seg_off ? seg_off[g + 1] : 1u;
-      apply_row<64, VEC, OP, BASIC, (GATED ? false : true)>(tv, row_ptr(tv, r), true, lane, values,
+      apply_row<64, VEC, OP, BASIC, (GATED ? false : true)>(tv, row_ptr(tv, pl.r), true, lane, values,
                                                             seg_off ? seg_pos : nullptr, q0, q1, g, a);
       if (OP == kOpReinit && lane == 0) {
         if (seg_off) {
@@ -1546,15 +1620,9 @@ __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t
         }
       }
     }
-    if (SOLO) __syncthreads();  // (lane 0 alone touches q, path and the buckets)
+    if (SOLO) __syncthreads();
   }
-  if (GATED) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (lane == 0)
-      __hip_atomic_store(&tv.ctr->n_pending, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    if (lane == 0) tv.ctr->n_pending = 0;
-  }
+  slow_pass_done<GATED>(tv, lane);
 }
 // ---------------------------------------------------------------------------------------------
 // The displacement pass with W wavefronts of ONE workgroup working on W pending ids at a time
@@ -1654,7 +1722,7 @@ __device__ __forceinline__ void slowpath_par_role(const TableView& tv, const int
     const bool active = i < np;
     const uint32_t g = active ? pending[i] : 0u;
     const int64_t id = active ? ids[g] : 0;
-    uint32_t r;   // (lane 0's value; left uninitialised on the other path: see slowpath_role)
+    uint32_t r;   // (lane 0's value; left uninitialised on the other path: see slow_place)
     if (active && lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
     int state = active ? 0 : 2;   // 0 to place, 1 placed, 2 nothing to do / failed
     int attempts = 0;
@@ -1664,11 +1732,7 @@ __device__ __forceinline__ void slowpath_par_role(const TableView& tv, const int
         have = (++attempts <= 64) ? wave_plan_slot(tv.buckets, tv.hp, id, L.q[w], L.path[w], lane, &depth) : 0;
         if (!have) {   // no path of length <= 5: the key is not inserted (reported at the next call)
           state = 2;
-          if (lane == 0) {
-            atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));
-            atomicOr(&tv.ctr->error, 1u);
-            atomicAdd(&tv.ctr->n_dropped, 1u);
-          }
+          if (lane == 0) slow_give_back(tv);
         }
       }
       if (lane == 0) {
@@ -1764,7 +1828,9 @@ __global__ __launch_bounds__(256) void restore_rows_kernel(TableView tv,
     for (uint32_t e = j; e < tv.row_floats; e += G) rp[e] = vp[e];
   }
 }
-// displacement pass of a restore: ids[pending[i]] get a slot, then the whole row
+// displacement pass of a restore: ids[pending[i]] get a slot, then the whole row.  Not slow_place: the
+// handle is reserved after a successful search (a failed restore strands none: rows_allocated shows
+// the order), and the timestamp is the id's own.
 __global__ __launch_bounds__(64) void restore_slowpath_kernel(TableView tv,
                                                               const int64_t* __restrict__ ids,
                                                               const float* __restrict__ values,
@@ -1785,8 +1851,7 @@ __global__ __launch_bounds__(64) void restore_slowpath_kernel(TableView tv,
         b->row[pos & 3] = r;
         b->ts[pos & 3] = ts[g];
       } else {
-        atomicOr(&tv.ctr->error, 1u);
-        atomicAdd(&tv.ctr->n_dropped, 1u);
+        slow_report_drop(tv);
       }
     }
     r = __shfl(r, 0);
@@ -1797,7 +1862,7 @@ __global__ __launch_bounds__(64) void restore_slowpath_kernel(TableView tv,
     }
     __syncthreads();
   }
-  if (lane == 0) tv.ctr->n_pending = 0;
+  slow_pass_done<false>(tv, lane);
 }
 
 // =============================================================================================

@@ -64,15 +64,13 @@ typedef const MHTE_CONST TableView* ConstViews;
   }
 // true when shape code `code` belongs to the instance of lane width VW
 #define MHTE_SHAPE_IS(VW, code) ((((code) & 1u) != 0u) == ((VW) == 1))
-// (segment kernels only) bit 1 of a shape code: the table has a whole-segment optimizer (GroupAdaGrad,
-// group_adagrad_segment) — served by the GROUP instance of seg_upsert_kernel / shard_upsert_kernel
-constexpr uint32_t kShapeGroupBit = 2u;
+// (segment kernels only) bit 1 of a shape code: kShapeGroupBit, mhte_kernels.h
 
 struct MStepStatic {
   RunView rv[2];           // run-dedup workspaces: slot s holds the batch deduplicated into it
                            // (ids / n / nblk are per launch: kernel arguments)
   float* grad_u;           // [n_max, dim] summed gradients of ids left to the displacement pass
-  uint32_t* pending;       // [n_max + 1]
+  uint32_t* pending;       // [n_max + 1] displacement list, one word per entry: unique index u
   float* part[2];          // per slot: partial rows of multi-item lists
   uint32_t* arrive[2];     // per slot: arrival counters, kept zeroed
   uint32_t* urow[2];       // per slot [n_max]: row handle of unique index u as the forward launch
@@ -645,7 +643,7 @@ struct SegUpsertArgs {
   ConstViews views;
   const int64_t* ids;
   const float* grads;
-  uint32_t* pending[kMaxStepTables];  // per table, 2 words per entry
+  uint32_t* pending[kMaxStepTables];  // per table, 2 words per entry: (position in `ids`, segment)
   uint32_t T;
   uint32_t seg0;
   uint32_t nseg;
@@ -714,7 +712,8 @@ __global__ __launch_bounds__(256, GROUP ? 1 : MHTE_SEGU_OCC) void seg_upsert_ker
 #undef MHTE_SEGU_CALL
 }
 
-// displacement pass of a fused optimize: one wavefront per table
+// displacement pass of a fused optimize, one wavefront per table: slow_place / apply_row_wave /
+// slow_pass_done (mhte_kernels.h) over the table's pending list, one entry per id
 __global__ __launch_bounds__(64) void seg_slow_kernel(SegUpsertArgs A) {
   __shared__ BfsSlot q[kMaxCuckooCount];
   __shared__ CuckooRecord path[kMaxBfsPathLen];
@@ -727,41 +726,13 @@ __global__ __launch_bounds__(64) void seg_slow_kernel(SegUpsertArgs A) {
   const ApplyArgs& a = A.a[t];
   for (uint32_t i = 0; i < np; ++i) {
     const uint32_t gp = pending[2 * i], seg = pending[2 * i + 1];
-    const int64_t id = A.ids[gp];
-    uint32_t r;  // (only lane 0's value is read, after the search: not merged with a constant on purpose,
-                 // slowpath_role)
-    if (lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
-    const long long pos = wave_insert_slot(tv.buckets, tv.hp, id, q, path, lane);
-    if (lane == 0) {
-      if (pos >= 0) {
-        Bucket* b = tv.buckets + (pos >> 2);
-        b->row[pos & 3] = r;
-        b->ts[pos & 3] = a.ts;
-      } else {
-        atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));
-        atomicOr(&tv.ctr->error, 1u);
-        atomicAdd(&tv.ctr->n_dropped, 1u);
-      }
-    }
-    r = __shfl(r, 0);
-    if (pos >= 0) {
-      const float* values = A.grads + size_t(A.grad_off[seg]);
-      const bool grp = (A.g[t] & kShapeGroupBit) != 0u;   // (rare path: both forms in one kernel)
-      if (A.g[t] & 1u) {
-        if (grp) apply_row<64, 1, kOpOptimize, false, true>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                            1u, int64_t(gp - A.id_off[seg]), a);
-        else apply_row<64, 1, kOpOptimize, false, false>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                         1u, int64_t(gp - A.id_off[seg]), a);
-      } else {
-        if (grp) apply_row<64, 4, kOpOptimize, false, true>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                            1u, int64_t(gp - A.id_off[seg]), a);
-        else apply_row<64, 4, kOpOptimize, false, false>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                         1u, int64_t(gp - A.id_off[seg]), a);
-      }
-    }
+    const SlowPlaced pl = slow_place(tv, A.ids[gp], a, q, path, lane);
+    if (pl.ok)
+      apply_row_wave<kOpOptimize, false>(tv, A.g[t], row_ptr(tv, pl.r), true, lane, A.grads + size_t(A.grad_off[seg]),
+                                         int64_t(gp - A.id_off[seg]), a);
     __syncthreads();
   }
-  if (lane == 0) tv.ctr->n_pending = 0;
+  slow_pass_done<false>(tv, lane);
 }
 
 }  // namespace mhte

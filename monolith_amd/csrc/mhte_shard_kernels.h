@@ -110,7 +110,8 @@ struct ShardOwnerArgs {
   // arrays below are indexed by the table's position in the launch, `views`, the header words and
   // the per-table device arrays by its index in the model
   uint32_t t0, tc;
-  uint32_t* pending[kMaxStepTables];
+  uint32_t* pending[kMaxStepTables];  // per table, 2 words per entry: (position in the peer block's table
+                                      // segment, peer — unused by the per-peer form)
   ShardTab tab[kMaxStepTables];
   uint8_t g[kMaxStepTables];          // lane-group shape per table (MHTE_SWITCH_G; | kShapeGroupBit)
   uint8_t count_hits[kMaxStepTables];
@@ -287,8 +288,9 @@ __global__ __launch_bounds__(512) void shard_lookup_kernel(ShardOwnerArgs A) {
 #undef MHTE_SEGL_CALL
 }
 
-// displacement pass of one peer's block for table t, by one wavefront (lane 0 alone touches q, path
-// and the buckets; the waits order its stores before the wavefront's next loads)
+// displacement pass of one peer's block for table t, by one wavefront beside the other tables' (the
+// per-peer owner form: tables with a filter): slow_place / apply_row_wave / slow_pass_done
+// (mhte_kernels.h), one entry per id
 __device__ __forceinline__ void shard_slow_role(const ShardOwnerArgs& A, uint32_t t, BfsSlot* q,
                                                 CuckooRecord* path, int lane) {
   const TableView& tv = deref_const(A.views + (A.t0 + t));
@@ -301,40 +303,12 @@ __device__ __forceinline__ void shard_slow_role(const ShardOwnerArgs& A, uint32_
   const ApplyArgs& a = A.a[t];
   for (uint32_t i = 0; i < np; ++i) {
     const uint32_t g = pending[2 * i];
-    const int64_t id = ids[g];
-    uint32_t r;  // (only lane 0's value is read, after the search: not merged with a constant on purpose,
-                 // slowpath_role)
-    if (lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
-    const long long pos = wave_insert_slot(tv.buckets, tv.hp, id, q, path, lane);
-    if (lane == 0) {
-      if (pos >= 0) {
-        Bucket* b = tv.buckets + (pos >> 2);
-        b->row[pos & 3] = r;
-        b->ts[pos & 3] = a.ts;
-      } else {
-        atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));
-        atomicOr(&tv.ctr->error, 1u);
-        atomicAdd(&tv.ctr->n_dropped, 1u);
-      }
-    }
-    r = __shfl(r, 0);
-    if (pos >= 0) {
-      const bool grp = (A.g[t] & kShapeGroupBit) != 0u;   // (rare path: both forms in one kernel)
-      if (A.g[t] & 1u) {
-        if (grp) apply_row<64, 1, kOpOptimize, false, true>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                            1u, int64_t(g), a);
-        else apply_row<64, 1, kOpOptimize, false, false>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                         1u, int64_t(g), a);
-      } else {
-        if (grp) apply_row<64, 4, kOpOptimize, false, true>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                            1u, int64_t(g), a);
-        else apply_row<64, 4, kOpOptimize, false, false>(tv, row_ptr(tv, r), true, lane, values, nullptr, 0u,
-                                                         1u, int64_t(g), a);
-      }
-    }
+    const SlowPlaced pl = slow_place(tv, ids[g], a, q, path, lane);
+    if (pl.ok)
+      apply_row_wave<kOpOptimize, false>(tv, A.g[t], row_ptr(tv, pl.r), true, lane, values, int64_t(g), a);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   }
-  if (lane == 0) tv.ctr->n_pending = 0;
+  slow_pass_done<false>(tv, lane);
 }
 
 // grid (x, tc): the block of peer A.peer.  Ids whose two buckets are full go to the table's pending
@@ -612,7 +586,8 @@ __global__ __launch_bounds__(256, GROUP ? 1 : ((MULTI && !FAST) ? MHTE_SEGX_OCC 
 // rank order, as the fast path would have applied them; then the headers of the step's send blocks are
 // cleared (the next numbering into them counts from zero).  Runs as the last launch of a step
 // (shard_slow_all_kernel) or — GATED — inside the NEXT owner lookup's launch, whose lookups of the table
-// wait for n_pending == 0 (slowpath_role's protocol: agent-scope release of the pass's stores, then the 0).
+// wait for n_pending == 0 (slow_pass_done<true>).  Per id: slow_place, then apply_row_wave once per sender
+// (mhte_kernels.h); the waits stand where a solo kernel has its barrier (slow_place).
 template <bool GATED>
 __device__ __forceinline__ void shard_slow_all_role(const ShardOwnerArgs& A, uint32_t t, const int64_t* recv_ids,
                                                     const float* rows, BfsSlot* q, CuckooRecord* path, int lane) {
@@ -625,23 +600,7 @@ __device__ __forceinline__ void shard_slow_all_role(const ShardOwnerArgs& A, uin
   for (uint32_t i = 0; i < np; ++i) {
     const uint32_t g = A.pending[t][2 * i], p = A.pending[t][2 * i + 1];
     const size_t eb = size_t(p) * A.geo.ids_block + tb.id_off;
-    const int64_t id = recv_ids[eb + g];
-    uint32_t r;  // (only lane 0's value is read, after the search: not merged with a constant on purpose,
-                 // slowpath_role)
-    if (lane == 0) r = static_cast<uint32_t>(atomicAdd(&tv.ctr->alloc, (1ull << 32) | 1ull));
-    const long long pos = wave_insert_slot(tv.buckets, tv.hp, id, q, path, lane);
-    if (lane == 0) {
-      if (pos >= 0) {
-        Bucket* b = tv.buckets + (pos >> 2);
-        b->row[pos & 3] = r;
-        b->ts[pos & 3] = a.ts;
-      } else {
-        atomicAdd(&tv.ctr->alloc, ~((1ull << 32) - 1ull));
-        atomicOr(&tv.ctr->error, 1u);
-        atomicAdd(&tv.ctr->n_dropped, 1u);
-      }
-    }
-    r = __shfl(r, 0);
+    const SlowPlaced pl = slow_place(tv, recv_ids[eb + g], a, q, path, lane);
     unsigned long long pm = 1ull << p;
     uint32_t* sl = nullptr;
     if (multi) {
@@ -654,28 +613,10 @@ __device__ __forceinline__ void shard_slow_all_role(const ShardOwnerArgs& A, uin
       pm &= pm - 1ull;
       const uint32_t sq = multi ? sl[kXKeyWords + k] - 1u : g;
       const float* values = rows + size_t(k) * A.geo.rows_block + tb.row_off;
-      if (pos >= 0) {
-        if (GATED) {
-          // (inside the lookup launch only tables of SGD / Adagrad / FTRL rows: the BASIC update code keeps
-          // that launch's registers — with all twelve optimizers it went from 54 to 143 VGPRs)
-          if (A.g[t] & 1u) apply_row<64, 1, kOpOptimize, true, false>(tv, row_ptr(tv, r), fresh, lane, values, nullptr,
-                                                                      0u, 1u, int64_t(sq), a);
-          else apply_row<64, 4, kOpOptimize, true, false>(tv, row_ptr(tv, r), fresh, lane, values, nullptr, 0u, 1u,
-                                                          int64_t(sq), a);
-        } else {
-          const bool grp = (A.g[t] & kShapeGroupBit) != 0u;   // (rare path: both forms in one kernel)
-          if (A.g[t] & 1u) {
-            if (grp) apply_row<64, 1, kOpOptimize, false, true>(tv, row_ptr(tv, r), fresh, lane, values, nullptr, 0u,
-                                                                1u, int64_t(sq), a);
-            else apply_row<64, 1, kOpOptimize, false, false>(tv, row_ptr(tv, r), fresh, lane, values, nullptr, 0u,
-                                                             1u, int64_t(sq), a);
-          } else {
-            if (grp) apply_row<64, 4, kOpOptimize, false, true>(tv, row_ptr(tv, r), fresh, lane, values, nullptr, 0u,
-                                                                1u, int64_t(sq), a);
-            else apply_row<64, 4, kOpOptimize, false, false>(tv, row_ptr(tv, r), fresh, lane, values, nullptr, 0u,
-                                                             1u, int64_t(sq), a);
-          }
-        }
+      if (pl.ok) {
+        // (GATED — inside the lookup launch — only tables of SGD / Adagrad / FTRL rows: the BASIC update code
+        // keeps that launch's registers — with all twelve optimizers it went from 54 to 143 VGPRs)
+        apply_row_wave<kOpOptimize, GATED>(tv, A.g[t], row_ptr(tv, pl.r), fresh, lane, values, int64_t(sq), a);
         fresh = false;
       }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -689,14 +630,7 @@ __device__ __forceinline__ void shard_slow_all_role(const ShardOwnerArgs& A, uin
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   }
-  if (np) {
-    if (GATED) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      if (lane == 0) __hip_atomic_store(&tv.ctr->n_pending, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (lane == 0) {
-      tv.ctr->n_pending = 0;
-    }
-  }
+  if (np) slow_pass_done<GATED>(tv, lane);
   if (A.zero_headers && uint32_t(lane) < world)
     A.clear_ids[size_t(lane) * A.geo.ids_block + A.t0 + t] = 0;
 }

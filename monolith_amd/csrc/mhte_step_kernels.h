@@ -1021,7 +1021,7 @@ __global__ __launch_bounds__(256) void rd_unreserve_kernel(const URec* __restric
 struct ApplyCtl {
   const float* grads;
   float* grad_u;          // [n_max, dim] summed gradients of ids deferred to the displacement pass
-  uint32_t* pending;
+  uint32_t* pending;      // displacement list, one word per entry: unique index u (defer_id)
   float* part;            // [items, dim] partial rows of multi-item lists
   uint32_t* arrive;       // [n] arrival counters, kept zeroed
   int64_t n_max;
@@ -2073,7 +2073,7 @@ __global__ __launch_bounds__(kExactThreads) void rd_exact_sum_kernel(RunView d, 
 // ---------------------------------------------------------------------------------------------
 // The two launches.
 // ---------------------------------------------------------------------------------------------
-struct SlowArgs {  // slowpath_role's arguments; enabled = 0: no displacement pass outstanding
+struct SlowArgs {  // slowpath_role's arguments (pending: one word per entry); enabled = 0: no pass outstanding
   const int64_t* uids;
   const float* grad_u;
   const uint32_t* pending;

@@ -111,15 +111,18 @@ def test_group_launch_count_does_not_grow_with_the_world(world, n_tables, expect
   assert steady[0] == expect, counts
 
 
-def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always_ahead=False, exact_order=False):
+def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always_ahead=False, exact_order=False,
+                          universe=None, ids_per_peer_table=0, check_tables=None):
+  """check_tables(mts): called with every rank's tables after the final comparison, before the group closes."""
   by_name = sorted(specs, key=lambda s: s.name)
-  universe = 200000 if dist == "uniform" else 7000
+  if universe is None:
+    universe = 200000 if dist == "uniform" else 7000
   exact = dist == "uniform" or exact_order   # every id occurs <= 32 times in a batch: sums in occurrence order
   mts = [make(specs) for _ in range(world)]
-  grp = ShardedStepGroup(mts, B)
+  grp = ShardedStepGroup(mts, B, ids_per_peer_table=ids_per_peer_table)
   if exact_order:
     grp.set_exact_order(True)
-  geo = shard_block_geometry(mts[0].get_table_dim_sizes(), B, world)
+  geo = shard_block_geometry(mts[0].get_table_dim_sizes(), B, world, ids_per_peer_table)
   info = _info_of(grp)
   assert (info[0], info[1], info[2]) == (geo["cap"], 8 * geo["ids_block"], 4 * geo["rows_block"])
   ots = {s.name: s.oracle_table() for s in specs}
@@ -183,8 +186,52 @@ def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always
         np.testing.assert_allclose(got, exp, rtol=RTOL, atol=ATOL)
     sizes = [int(mts[r].size(sp.name)) for r in range(world)]
     assert sum(sizes) == seen.size, (sp.name, sizes, seen.size)
+  if check_tables is not None:
+    check_tables(mts)
   grp.close()
   return launch_counts
+
+
+def _displaced_not_doubled(specs, slots):
+  """The three conditions of the other paths' high-load tests (test_multi_step_displacement_and_doubling),
+  for every rank and table: nothing dropped, the table never doubled, and it is over half full — ids
+  whose two buckets were full were placed by the displacement pass."""
+  def check(mts):
+    for r, mt in enumerate(mts):
+      for sp in specs:
+        st = mt.stats(sp.name)
+        assert st.dropped == 0, (r, sp.name, st.dropped)
+        assert st.hashpower == (slots // 4).bit_length() - 1, (r, sp.name, st.hashpower)
+        assert st.size > 0.5 * slots, (r, sp.name, st.size)
+  return check
+
+
+@pytest.mark.parametrize("world,group_opt", [(1, False), (3, False), (2, True)])
+def test_group_displacement_at_high_load(world, group_opt):
+  """The owner's displacement pass, forced: tables of 8192 slots (hashpower 11) that may fill to 0.97,
+  uniform ids, five steps that take every owner's tables to 5800-6700 ids (load 0.70-0.82; per-owner oracle
+  tables of 8192 slots hold them without doubling), so that every update past the first defers ids whose two
+  buckets are full.
+    world 1: basic optimizers, the pass rides in the next owner lookup (shard_slow_all_role<true>);
+    world 3: the pass as a launch of its own, deferred ids with entries of several senders in the
+             cross-peer slots (shard_slow_all_role<false>);
+    world 2, GroupAdaGrad tables: the whole-segment form of the 64-lane update (apply_row_wave's GROUP).
+  The tables must not double, and an owner reserves key capacity for full blocks from every peer before each
+  update (Table::ensure_capacity(cap * world)): live keys + cap * world has to stay under 0.97 * 8192 = 7946.
+  Hence B = 1600 ids per rank and table from a universe of 30000 per rank, and peer blocks of B / world + 100
+  ids (the largest block of these batches holds 578 of 636 at world 3, 834 of 900 at world 2): the bound peaks
+  at 7340.  Uniform ids: bit-exact against the oracle like test_group_against_oracle[uniform-*]."""
+  kw = dict(initial_capacity=1 << 13, max_load_factor=0.97)
+  if group_opt:
+    specs = group_opt_specs()
+    for sp in specs:
+      sp.kw = kw
+  else:
+    specs = dlrm_specs(3, **kw)
+  B = 1600
+  _group_against_oracle(specs, "uniform", world, False, B=B, steps=5, universe=30000 * world,
+                        ids_per_peer_table=B if world == 1 else B // world + 100,
+                        check_tables=_displaced_not_doubled(specs, 1 << 13))
 
 
 @pytest.mark.parametrize("world", [1, 3])
@@ -344,28 +391,36 @@ def test_overlap_over_rccl(monkeypatch):
   test_group_against_oracle("uniform", 2)      # (in-process groups ignore the mode)
 
 
-def test_sharded_step_with_occurrence_filters():
+@pytest.mark.parametrize("high_load", [False, True])
+def test_sharded_step_with_occurrence_filters(high_load):
   """Tables with an occurrence filter through the sharded step (round 2 rejected them): every OWNER
   asks its own filter about the ids of a sender's block it does not hold, with count 1 per (sender,
   id) — the reference's fused optimize behind the all-to-all (tf_bridge.cc:300-321 per id of
   multi_hash_table_update_op.cc:270-306) — senders in rank order, the window moving between them.
-  Checked against oracle tables + the filter restatement (oracle.SlidingFilter) per owner."""
+  Checked against oracle tables + the filter restatement (oracle.SlidingFilter) per owner.
+  high_load: tables of 1024 slots that may fill to 0.97 and never double, filled to 770-785 admitted ids per
+  owner and table (the oracle tables' sizes), so that the per-peer displacement pass (shard_slow_role) must
+  place ids.  An owner reserves key capacity for full blocks from every peer before each update
+  (Table::ensure_capacity(cap * world)), so the load is reached in small steps: 40 steps of 120 ids per rank
+  and table, peer blocks of 84 ids (the largest holds 73); live keys + 2 * 84 peaks at 940 of 0.97 * 1024 = 993."""
   from monolith_amd import entry
   from monolith_amd.multi_hash_table_ops import HashFilter, MultiHashTable
-  world, B, steps, thr = 2, 1500, 6, 2
+  world, thr = 2, 2
+  B, steps, cap = (120, 40, 84) if high_load else (1500, 6, 0)
   dims = {"a": 16, "b": 32}
   mts, flts, ots, models = [], [], [], []
   for r in range(world):
     flt = HashFilter(capacity=4000, split_num=5)
     cfgs = {n: entry.make_table_config(
         [entry.CombineAsSegment(d, entry.ZerosInitializer(), entry.AdagradOptimizer(0.05, 0.1))],
+        entry.CuckooHashTableConfig(**(dict(initial_capacity=1 << 10, max_load_factor=0.97) if high_load else {})),
         slot_occurrence_threshold_config=entry.SlotOccurrenceThresholdConfig(default_occurrence_threshold=thr))
             for n, d in dims.items()}
     mts.append(MultiHashTable.from_configs(cfgs, name_suffix="shflt%d" % r, hash_filter=flt))
     flts.append(flt)
     ots.append({n: O.Table(O.segment(d, O.OPT_ADAGRAD, p=(0.1, 0.0)), 1) for n, d in dims.items()})
     models.append(O.SlidingFilter(4000, 5, defer_advance=True))
-  grp = ShardedStepGroup(mts, B)
+  grp = ShardedStepGroup(mts, B, ids_per_peer_table=cap)
   names = sorted(dims)
   dropped = [0]
 
@@ -374,6 +429,12 @@ def test_sharded_step_with_occurrence_filters():
     # filter signature (fid bits 17..28, hash_filter.h:151), so no two ids share a count: which of two
     # aliasing ids of ONE launch crosses the threshold first is not defined (nor in the reference,
     # whose filter is not thread safe) and would make the expectation order-dependent.
+    if high_load:
+      # (the ids below reach 430-580 per owner and table — id_batch's fids collide modulo 1800 and the low
+      # bits favour owner 0 — which no table size holds both over half full and under 0.97; here every
+      # index comes and the owners get half each)
+      idx = np.random.default_rng(50 * s + 7 * r + k).integers(0, 1700, B) + 1800 * k
+      return ((idx + 1) << 17) | (idx % 2) | (np.int64(k + 1) << 48)
     idx = S.id_batch(50 * s + 7 * r + k, B, 1800, "uniform") % 1800 + 1800 * k
     return ((idx + 1) << 17) | (idx % 7) | (np.int64(k + 1) << 48)
 
@@ -440,6 +501,11 @@ def test_sharded_step_with_occurrence_filters():
     if absent.any():
       np.testing.assert_array_equal(flts[o].get(torch.as_tensor(probe[absent]).cuda()).cpu().numpy(),
                                     [models[o].get(int(x)) for x in probe[absent]])
+  if high_load:
+    for o in range(world):
+      for n in names:
+        st = mts[o].stats(n)
+        assert st.dropped == 0 and st.hashpower == 8 and st.size > 0.5 * (1 << 10), (o, n, st.size, st.hashpower)
   grp.close()
 
 
