@@ -321,6 +321,64 @@ mhte_status mhte_fused_gather_embeddings_by_input_gradient(float* fused_grad, in
 mhte_status mhte_reduce_rows(const int64_t* indices, const float* values, int64_t n, int32_t dim,
                              int64_t batch, int32_t mode, int32_t indices_sorted, float* out,
                              void* stream);
+/* MonolithFusedGatherEmbeddingsByInputGradient with the reference's `scale` INPUT left where synchronous
+ * GPU training computes it (NT/distributed_ps_sync.py:313-331: min(clip_norm / global_norm, 1), a tensor):
+ * scale_dev [dev f32, 1] is read once at the top of every kernel (a uniform load); per addend the same arithmetic as the entry point
+ * above called with that value (acc + x * scale), the same launches.  Nothing reaches the host, and a
+ * captured graph replays with whatever the word holds then. */
+mhte_status mhte_fused_gather_embeddings_by_input_gradient_dev_scale(float* fused_grad, int64_t fused_len,
+                                                                     int32_t n_inputs,
+                                                                     const float* const* grads,
+                                                                     const int32_t* const* offsets,
+                                                                     const int64_t* n, const int32_t* dims,
+                                                                     const float* scale_dev, void* stream);
+
+/* ---- clip by global norm (csrc/mhte_clip_kernels.h) ------------------------------------------------
+ * GlobalL2Reduce, MonolithClipByGlobalNorm, MonolithClipByGlobalNormFused (RT/ops/clip_by_global_norm.h
+ * :31-60, clip_by_global_norm_op.cc, clip_by_global_norm.cu.cc, clip_by_global_norm_fused.cu.cc:37-165;
+ * NT/clip_ops.py:25-80; the default gradient clip of NT/feature_utils.py:211-264).
+ *   tensors / inputs / outputs   HOST arrays of n device pointers (fp32); lens HOST [n], floats per tensor
+ *                                (int64: no 2^31 cap; 0 is legal, its pointer is not looked at)
+ *   result                       [dev f32, 4]: [0] sum of squares, [1] norm = sqrt([0]), [2] scale =
+ *                                norm > clip_norm ? clip_norm / norm : 1 (clip_by_global_norm.h:42-43),
+ *                                [3] 0.  A NaN norm gives scale 1, an infinite one scale 0 (the clipped
+ *                                values are then NaN, as NT/clip_ops_test.py:53-58 expects).
+ * The sum of squares is one fixed tree over chunks of 4096 consecutive floats per tensor — 1024 partial
+ * sums, each a thread-serial chain over its chunks followed by halvings, then halvings of the partials;
+ * products and sums rounded to fp32 one by one, no FMA, no float atomics (the reference's GPU kernels add
+ * block sums with atomicAdd: other bits every run) — so the result depends on the tensors' contents,
+ * lengths and order only, not on the grid, the device or the run.  tests/clip_ops_truth.py restates it.
+ * The scale stays in HBM: the fused form sums the partials again in the prologue of its second launch
+ * (the reference waits for the stream there, clip_by_global_norm_fused.cu.cc:150), and result + 2 is what
+ * mhte_scale_tensors_dev and mhte_fused_gather_embeddings_by_input_gradient_dev_scale take.  No entry
+ * point waits for the device or reads a device value; the partials live in the per-device auxiliary
+ * workspace (allocated by the first call; calls on several streams are ordered by events).  Up to 128
+ * non-empty tensors travel in the kernel arguments; more are uploaded per call (any number; such a call
+ * cannot be captured into a graph).  out[i] == in[i] is allowed; an in-place tensor is not touched at
+ * all when the scale is exactly 1 ("no clip: the outputs are the inputs"), any other is copied.
+ * 16-byte accesses where a pointer is 16-byte aligned, else 4-byte ones (same bits).
+ * InvalidArgument, checked on the host before any device call, the entry point's name in the message: a
+ * null argument, n < 0, a negative length, a null pointer for a non-empty tensor, clip_norm negative or
+ * NaN.  n = 0 is legal: sum 0, norm 0, scale 1.
+ *   mhte_global_l2_reduce           GlobalL2Reduce + the deferred scale (feature_utils' cond_defer_clip);
+ *                                   clip_norm = +inf: the norm alone.  Two launches.
+ *   mhte_clip_by_global_norm        MonolithClipByGlobalNorm with the norm on the host: one launch, none
+ *                                   for in-place tensors when global_norm <= clip_norm
+ *   mhte_clip_by_global_norm_dev    the same with the norm in a device word: one launch
+ *   mhte_clip_by_global_norm_fused  MonolithClipByGlobalNormFused: two launches, no wait between them
+ *   mhte_scale_tensors_dev          out[i] = in[i] * *scale_dev for all tensors in one launch (the
+ *                                   multiply NT/distribution_ops.py:535-549 does per layout tensor with
+ *                                   layout_tensors_grad_scale before fused_embedding_to_layout_grad) */
+mhte_status mhte_global_l2_reduce(const float* const* tensors, const int64_t* lens, int32_t n, float clip_norm,
+                                  float* result, void* stream);
+mhte_status mhte_clip_by_global_norm(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                     int32_t n, float global_norm, float clip_norm, void* stream);
+mhte_status mhte_clip_by_global_norm_dev(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                         int32_t n, const float* global_norm_dev, float clip_norm, void* stream);
+mhte_status mhte_clip_by_global_norm_fused(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                           int32_t n, float clip_norm, float* result, void* stream);
+mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                   int32_t n, const float* scale_dev, void* stream);
 
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the

@@ -36,6 +36,7 @@
 #include <map>
 #include "mhte_pool_kernels.h"
 #include "mhte_pool_split_kernels.h"
+#include "mhte_clip_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
@@ -2119,6 +2120,8 @@ struct AuxWs {
   DedupWs dd;
   DevBuf<int64_t> keys, uids;
   DevBuf<uint32_t> inverse, seg_off, seg_pos, nu;
+  DevBuf<float> clip_partials;   // clip by global norm (mhte_clip_host.h): the 1024 partial sums of squares
+  DevBuf<char> clip_table;       // ... and the tensor table of a call with more than 128 tensors
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;
@@ -2144,11 +2147,22 @@ struct AuxWs {
     used = true;
   }
   void leave(hipStream_t st) { HIP_OK(hipEventRecord(done, st)); }   // after the call's last launch
+  // A stream that is being captured into a graph takes neither the wait nor the record: the graph's own
+  // edges order its launches, and an event the capture has touched must not be waited for by a later call
+  // outside it.  Whoever replays such a graph beside calls on another stream orders the two themselves.
   struct Use {   // enter now, leave when the caller's launches are enqueued
     AuxWs& ws;
     hipStream_t st;
-    Use(AuxWs& w, hipStream_t s) : ws(w), st(s) { ws.enter(st); }
-    ~Use() { (void)hipEventRecord(ws.done, st); }
+    bool capturing = false;
+    Use(AuxWs& w, hipStream_t s) : ws(w), st(s) {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+      capturing = cs == hipStreamCaptureStatusActive;
+      if (!capturing) ws.enter(st);
+    }
+    ~Use() {
+      if (!capturing) (void)hipEventRecord(ws.done, st);
+    }
   };
   // The same lists for keys known to lie in [0, 2^key_bits), key_bits <= 31: a STABLE radix sort of
   // (key, position) pairs — equal keys keep their positions ascending — and the heads of the sorted runs
@@ -2277,7 +2291,8 @@ static int current_device() {
 template <bool GATHER>
 static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* offsets,
                          const int64_t* n, const int32_t* dims, float* const* rows, float scale,
-                         hipStream_t st, int64_t fused_len = int64_t(1) << 31, bool zeroed = false) {
+                         hipStream_t st, int64_t fused_len = int64_t(1) << 31, bool zeroed = false,
+                         const float* scale_dev = nullptr) {
   if (n_inputs < 0) throw Error(MHTE_INVALID_ARGUMENT, "n_inputs must be >= 0");
   int key_bits = 1;   // (offsets are int32 and lie inside the fused buffer)
   while (key_bits < 31 && (int64_t(1) << key_bits) < fused_len) ++key_bits;
@@ -2309,21 +2324,38 @@ static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* o
       ws.group_sorted(ws.keys.p, acc, key_bits, st);   // (a key is a float offset into the fused buffer)
       bool vec = in.aligned != 0;
       for (int32_t k = 0; k < in.n_inputs; ++k) vec = vec && (in.dim[k] & 3) == 0;
-      if (vec)
-        gather_grad_lists_vec_kernel<<<dim3(uint32_t(((acc + kGatherGradKeys - 1) / kGatherGradKeys * 16 + 255) / 256)), 256, 0, st>>>(
-            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p, (zeroed && i0 == 0) ? 1 : 0);
+      // (scale_dev: the factor is a device word, read by every workgroup — the same kernels otherwise)
+      const dim3 gv(uint32_t(((acc + kGatherGradKeys - 1) / kGatherGradKeys * 16 + 255) / 256)), gs(uint32_t((acc * 8 + 255) / 256));
+      const int fresh = (zeroed && i0 == 0) ? 1 : 0;
+      if (vec && !scale_dev)
+        gather_grad_lists_vec_kernel<false><<<gv, 256, 0, st>>>(
+            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p, fresh, nullptr);
+      else if (vec)
+        gather_grad_lists_vec_kernel<true><<<gv, 256, 0, st>>>(
+            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p, fresh, scale_dev);
+      else if (!scale_dev)
+        gather_grad_lists_kernel<false><<<gs, 256, 0, st>>>(
+            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p, nullptr);
       else
-        gather_grad_lists_kernel<<<dim3(uint32_t((acc * 8 + 255) / 256)), 256, 0, st>>>(
-            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p);
+        gather_grad_lists_kernel<true><<<gs, 256, 0, st>>>(
+            fused, in, scale, ws.uids.p, ws.nu.p, ws.seg_off.p, ws.seg_pos.p, scale_dev);
       HIP_OK(hipGetLastError());
       continue;
     }
     const dim3 grid(uint32_t((acc * 8 + 255) / 256));
-    fused_gather_kernel<GATHER><<<grid, 256, 0, st>>>(fused, in, scale);
+    if constexpr (!GATHER) {   // (the forward gather has no scale: no <true, true> instantiation)
+      if (scale_dev) {
+        fused_gather_kernel<false, true><<<grid, 256, 0, st>>>(fused, in, scale, scale_dev);
+        HIP_OK(hipGetLastError());
+        continue;
+      }
+    }
+    fused_gather_kernel<GATHER, false><<<grid, 256, 0, st>>>(fused, in, scale, nullptr);
     HIP_OK(hipGetLastError());
   }
 }
 }  // namespace mhte
+#include "mhte_clip_host.h"
 }  // extern "C++"
 
 mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
@@ -2336,6 +2368,27 @@ mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings,
   });
 }
 
+}  // extern "C"
+namespace mhte {
+// scale_dev != NULL: the factor is read on the device (scale is then not used)
+static void fused_gather_gradient(float* fused_grad, int64_t fused_len, int32_t n_inputs, const float* const* grads,
+                                  const int32_t* const* offsets, const int64_t* n, const int32_t* dims, float scale,
+                                  const float* scale_dev, hipStream_t st) {
+  if (fused_len < 0) throw Error(MHTE_INVALID_ARGUMENT, "fused_len must be >= 0");
+  if (fused_len) {   // (16-byte stores from a full grid: hipMemsetAsync moves a large buffer at 1.3 TB/s)
+    LayoutZeroArgs Z{};
+    Z.p[0] = fused_grad;
+    Z.len[0] = uint64_t(fused_len);
+    const uint32_t gx = uint32_t(std::min<uint64_t>(2048, (uint64_t(fused_len) + 4095) / 4096));
+    layout_zero_args_kernel<<<dim3(gx, 1), 256, 0, st>>>(Z);
+    HIP_OK(hipGetLastError());
+  }
+  fused_gather<false>(fused_grad, n_inputs, offsets, n, dims, const_cast<float* const*>(grads), scale, st,
+                      fused_len > 0 ? fused_len : 1, /*zeroed=*/fused_len > 0, scale_dev);
+}
+}  // namespace mhte
+extern "C" {
+
 mhte_status mhte_fused_gather_embeddings_by_input_gradient(float* fused_grad, int64_t fused_len,
                                                            int32_t n_inputs,
                                                            const float* const* grads,
@@ -2343,17 +2396,101 @@ mhte_status mhte_fused_gather_embeddings_by_input_gradient(float* fused_grad, in
                                                            const int64_t* n, const int32_t* dims,
                                                            float scale, void* stream) {
   return guard([&] {
-    if (fused_len < 0) throw Error(MHTE_INVALID_ARGUMENT, "fused_len must be >= 0");
-    if (fused_len) {   // (16-byte stores from a full grid: hipMemsetAsync moves a large buffer at 1.3 TB/s)
-      LayoutZeroArgs Z{};
-      Z.p[0] = fused_grad;
-      Z.len[0] = uint64_t(fused_len);
-      const uint32_t gx = uint32_t(std::min<uint64_t>(2048, (uint64_t(fused_len) + 4095) / 4096));
-      layout_zero_args_kernel<<<dim3(gx, 1), 256, 0, S(stream)>>>(Z);
-      HIP_OK(hipGetLastError());
-    }
-    fused_gather<false>(fused_grad, n_inputs, offsets, n, dims, const_cast<float* const*>(grads),
-                        scale, S(stream), fused_len > 0 ? fused_len : 1, /*zeroed=*/fused_len > 0);
+    fused_gather_gradient(fused_grad, fused_len, n_inputs, grads, offsets, n, dims, scale, nullptr, S(stream));
+  });
+}
+
+mhte_status mhte_fused_gather_embeddings_by_input_gradient_dev_scale(float* fused_grad, int64_t fused_len,
+                                                                     int32_t n_inputs,
+                                                                     const float* const* grads,
+                                                                     const int32_t* const* offsets,
+                                                                     const int64_t* n, const int32_t* dims,
+                                                                     const float* scale_dev, void* stream) {
+  return guard([&] {
+    if (!scale_dev)
+      throw Error(MHTE_INVALID_ARGUMENT, "fused_gather_embeddings_by_input_gradient_dev_scale: null argument: scale_dev");
+    fused_gather_gradient(fused_grad, fused_len, n_inputs, grads, offsets, n, dims, 1.f, scale_dev, S(stream));
+  });
+}
+
+// ---- clip by global norm (csrc/mhte_clip_kernels.h, mhte_clip_host.h) --------------------------------
+mhte_status mhte_global_l2_reduce(const float* const* tensors, const int64_t* lens, int32_t n, float clip_norm,
+                                  float* result, void* stream) {
+  return guard([&] {
+    const char* op = "global_l2_reduce";
+    if (!tensors) clip_bad(op, "null argument: tensors");
+    if (!lens) clip_bad(op, "null argument: lens");
+    if (!result) clip_bad(op, "null argument: result");
+    clip_check(op, tensors, "tensors", nullptr, lens, n, true, clip_norm);
+    clip_need_device();
+    ClipTable T;
+    clip_build(T, op, tensors, nullptr, lens, n, false);
+    clip_norm_launch(T, clip_norm, result, /*fused=*/false, S(stream));
+  });
+}
+
+mhte_status mhte_clip_by_global_norm(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                     int32_t n, float global_norm, float clip_norm, void* stream) {
+  return guard([&] {
+    const char* op = "clip_by_global_norm";
+    if (!inputs) clip_bad(op, "null argument: inputs");
+    if (!outputs) clip_bad(op, "null argument: outputs");
+    if (!lens) clip_bad(op, "null argument: lens");
+    clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
+    clip_need_device();
+    // clip_by_global_norm.h:42-43 on the host; not clipped: tensors that are in place take no part at all
+    const float scale = global_norm > clip_norm ? clip_norm / global_norm : 1.0f;
+    ClipTable T;
+    clip_build(T, op, inputs, outputs, lens, n, /*skip_inplace=*/scale == 1.0f);
+    clip_scale_launch(T, kClipScaleArg, scale, nullptr, clip_norm, S(stream));
+  });
+}
+
+mhte_status mhte_clip_by_global_norm_dev(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                         int32_t n, const float* global_norm_dev, float clip_norm, void* stream) {
+  return guard([&] {
+    const char* op = "clip_by_global_norm_dev";
+    if (!inputs) clip_bad(op, "null argument: inputs");
+    if (!outputs) clip_bad(op, "null argument: outputs");
+    if (!lens) clip_bad(op, "null argument: lens");
+    if (!global_norm_dev) clip_bad(op, "null argument: global_norm_dev");
+    clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
+    clip_need_device();
+    ClipTable T;
+    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_scale_launch(T, kClipScaleNorm, 1.f, global_norm_dev, clip_norm, S(stream));
+  });
+}
+
+mhte_status mhte_clip_by_global_norm_fused(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                           int32_t n, float clip_norm, float* result, void* stream) {
+  return guard([&] {
+    const char* op = "clip_by_global_norm_fused";
+    if (!inputs) clip_bad(op, "null argument: inputs");
+    if (!outputs) clip_bad(op, "null argument: outputs");
+    if (!lens) clip_bad(op, "null argument: lens");
+    if (!result) clip_bad(op, "null argument: result");
+    clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
+    clip_need_device();
+    ClipTable T;
+    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_norm_launch(T, clip_norm, result, /*fused=*/true, S(stream));
+  });
+}
+
+mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* outputs, const int64_t* lens,
+                                   int32_t n, const float* scale_dev, void* stream) {
+  return guard([&] {
+    const char* op = "scale_tensors_dev";
+    if (!inputs) clip_bad(op, "null argument: inputs");
+    if (!outputs) clip_bad(op, "null argument: outputs");
+    if (!lens) clip_bad(op, "null argument: lens");
+    if (!scale_dev) clip_bad(op, "null argument: scale_dev");
+    clip_check(op, inputs, "inputs", outputs, lens, n, false, 0.f);
+    clip_need_device();
+    ClipTable T;
+    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_scale_launch(T, kClipScaleWord, 1.f, scale_dev, 0.f, S(stream));
   });
 }
 

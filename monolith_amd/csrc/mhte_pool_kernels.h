@@ -68,9 +68,13 @@ __global__ __launch_bounds__(256) void lookup_gradient_kernel(const int64_t* __r
   }
 }
 
-template <bool GATHER>
+// DEVSCALE (gradient only): the factor is the device word scale_dev — a clip scale that never left HBM
+// (mhte_clip_kernels.h) — one uniform load at the top of the kernel (every wavefront issues it, no thread
+// reads it again); the arithmetic per addend is the same.
+template <bool GATHER, bool DEVSCALE>
 __global__ __launch_bounds__(256) void fused_gather_kernel(float* __restrict__ fused, GatherInputs in,
-                                                           float scale) {
+                                                           float scale, const float* __restrict__ scale_dev) {
+  if (DEVSCALE) scale = *(const MHTE_GLOBAL float*)(scale_dev);
   constexpr int G = 8;
   const int j = threadIdx.x & (G - 1);
   const int64_t r = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;
@@ -260,13 +264,15 @@ constexpr int kGatherGradKeys = 4;   // keys a lane group works on at once (thei
 // fresh: the fused buffer is known to be all zeros (the entry point has just filled it and this is its first
 // launch): a destination is then stored without being read first — 0 + acc is acc bit for bit, a sum that
 // started as 0 + x is never -0 — a third of the launch's bytes (round 6: 126 -> ~100 us for 1 M keys).
+template <bool DEVSCALE>
 __global__ __launch_bounds__(256) void gather_grad_lists_vec_kernel(float* __restrict__ fused, GatherInputs in,
                                                                     float scale,
                                                                     const int64_t* __restrict__ keys,
                                                                     const uint32_t* __restrict__ n_keys,
                                                                     const uint32_t* __restrict__ seg_off,
                                                                     const uint32_t* __restrict__ seg_pos,
-                                                                    int fresh) {
+                                                                    int fresh, const float* __restrict__ scale_dev) {
+  if (DEVSCALE) scale = *(const MHTE_GLOBAL float*)(scale_dev);
   constexpr int G = 16, K = kGatherGradKeys;
   __shared__ long long s_start[kMaxGatherInputs + 1];
   __shared__ const float* s_rows[kMaxGatherInputs];
@@ -382,12 +388,15 @@ __global__ __launch_bounds__(256) void gather_grad_lists_vec_kernel(float* __res
     }
   }
 }
+template <bool DEVSCALE>
 __global__ __launch_bounds__(256) void gather_grad_lists_kernel(float* __restrict__ fused, GatherInputs in,
                                                                 float scale,
                                                                 const int64_t* __restrict__ keys,
                                                                 const uint32_t* __restrict__ n_keys,
                                                                 const uint32_t* __restrict__ seg_off,
-                                                                const uint32_t* __restrict__ seg_pos) {
+                                                                const uint32_t* __restrict__ seg_pos,
+                                                                const float* __restrict__ scale_dev) {
+  if (DEVSCALE) scale = *(const MHTE_GLOBAL float*)(scale_dev);
   constexpr int G = 8;
   const int j = threadIdx.x & (G - 1);
   const int64_t u = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;

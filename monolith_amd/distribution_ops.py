@@ -272,14 +272,24 @@ def fused_gather_embeddings_by_input(fused_embeddings: torch.Tensor,
 
 def fused_gather_embeddings_by_input_gradient(fused_embeddings_size: int, grads: List[torch.Tensor],
                                               embedding_offsets: List[torch.Tensor],
-                                              embedding_dims: List[int], scale: float = 1.0):
-  """reference :678-686: the flat gradient of the fused buffer (float atomics, like the reference)."""
+                                              embedding_dims: List[int], scale=1.0):
+  """reference :678-686: the flat gradient of the fused buffer (float atomics, like the reference).
+  ``scale``: a Python float, or a 0-d float32 device tensor (``clip_ops.global_norm_and_scale``) that is
+  read on the device — nothing comes back to the host and a captured graph replays with its current value."""
   dev = grads[0].device
   offs = [o.to(device=dev, dtype=torch.int32).contiguous() for o in embedding_offsets]
   gs = [g.to(device=dev, dtype=torch.float32).contiguous() for g in grads]
   out = torch.empty(int(fused_embeddings_size), dtype=torch.float32, device=dev)
   n = (C.c_int64 * len(offs))(*[o.numel() for o in offs])
   dims = (C.c_int32 * len(offs))(*[int(d) for d in embedding_dims])
+  if isinstance(scale, torch.Tensor):
+    if not (scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1):
+      raise TypeError("fused_gather_embeddings_by_input_gradient: scale must be a float or a 0-d float32 "
+                      "tensor on the GPU")
+    check(_lib.lib().mhte_fused_gather_embeddings_by_input_gradient_dev_scale(
+        vp(out), out.numel(), len(offs), _ptr_array(gs), _ptr_array(offs), n,
+        dims, vp(scale), _stream()))
+    return out
   check(_lib.lib().mhte_fused_gather_embeddings_by_input_gradient(
       vp(out), out.numel(), len(offs), _ptr_array(gs), _ptr_array(offs), n,
       dims, scale, _stream()))
