@@ -611,7 +611,12 @@ mhte_status mhte_table_optimize_n(mhte_multi_table* t, int32_t table, const int6
  *                   with the reference); otherwise lists of > 32 occurrences are summed in
  *                   256-entry chunks in a fixed association (deterministic; fp32 re-association
  *                   only).  MHTE_DEFER_SLOWPATH: do not launch the displacement pass for ids whose
- *                   two buckets are full; see mhte_table_finish_pending. */
+ *                   two buckets are full; see mhte_table_finish_pending.
+ * Alignment: grads and grad_unique need 4-byte alignment only.  The one-launch form moves a row as
+ * float4s when both are 16-byte aligned and one float per lane otherwise, which covers rows of up to
+ * 64 floats; a wider row in a buffer that is not 16-byte aligned takes the route of the rows too wide
+ * for the fused kernel (segment sum + update of the unique ids: the lists must then be the CSR lists of
+ * mhte_unique, MHTE_INVALID_ARGUMENT otherwise).  Same result either way. */
 enum { MHTE_EXACT_ORDER = 1, MHTE_DEFER_SLOWPATH = 2 };
 mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_dedup_ws* ws,
                                       const int64_t* unique_ids, int64_t n_max,
@@ -651,7 +656,13 @@ mhte_status mhte_table_finish_pending(mhte_multi_table* t, int32_t table, void* 
  *                  tree over position ranges (deterministic; fp32 re-association only)
  * The first batch of a pipeline is deduplicated by mhte_step_dedup.  The displacement pass left
  * by step_backward is run by the next step_forward, or by any other call on the table
- * (mhte_table_finish_pending).  The table row must satisfy mhte_table_fused_backward_ok. */
+ * (mhte_table_finish_pending).  The table row must satisfy mhte_table_fused_backward_ok.
+ * Alignment: embedding (step_forward), grads and grad_unique (step_backward) of a table whose row has
+ * more than 64 floats must be 16-byte aligned: these launches give a row one lane group and move it as
+ * float4s only.  Anything else is MHTE_INVALID_ARGUMENT, raised before the call changes anything (the
+ * next batch's dedup is not begun, the queued displacement pass and the workspaces stay as they were:
+ * the call can be repeated with aligned buffers).  Rows of up to 64 floats take any 4-byte aligned
+ * buffer (one float per lane). */
 mhte_status mhte_step_dedup(mhte_dedup_ws* ws, const int64_t* id, int64_t n, int64_t* unique_ids,
                             uint32_t* n_unique_dev, void* stream);
 /* Sender side of the id-sharded step (NT/distributed_ps_sync.py:95-490), on the batch held by ws
@@ -692,7 +703,9 @@ mhte_status mhte_table_step_backward(mhte_multi_table* t, int32_t table, mhte_de
  * The forward launch of a step whose batch was deduplicated this way carries the lookups alone
  * (mhte_table_step_forward with ws_next NULL): ~4 us less per step at 65 536 ids.  The reference's
  * pipeline prefetches the same way, one stage queue per step of look-ahead
- * (NT/distributed_ps_sync.py:199-203,270-275).  ws_ahead NULL: exactly mhte_table_step_backward. */
+ * (NT/distributed_ps_sync.py:199-203,270-275).  ws_ahead NULL: exactly mhte_table_step_backward.
+ * The alignment rule of mhte_table_step_backward holds: a refused call has not begun the dedup of
+ * id_ahead either. */
 mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, mhte_dedup_ws* ws,
                                            mhte_dedup_ws* ws_next, const int64_t* unique_ids,
                                            int64_t n_max, const uint32_t* n_unique_dev,

@@ -21,6 +21,7 @@
 #include <exception>
 #include <mutex>
 #include <future>
+#include <initializer_list>
 #include <thread>
 #include <stdexcept>
 #include <string>
@@ -1105,9 +1106,40 @@ struct Table {
       if (view.seg[i].opt == kOptGroupAdagrad) return false;
     return fusable_shape();
   }
-  bool fusable_shape() const {   // the row fits one lane group
+  bool fusable_shape() const {   // the row fits one lane group (of float4 lanes, where the row has them)
     Shape sh = pick_shape(dim, vec_ok);
     return dim <= uint32_t(sh.G * sh.VEC);
+  }
+  // The lane shape of a fused launch (sum_apply / step_fwd / step_bwd) for the buffers of THIS call:
+  // float4 lanes need every one of them 16-byte aligned.  The fused kernels give a row ONE lane group
+  // and do not loop over its columns, so a float4 table of more than 64 floats per row has no shape
+  // for a buffer that is only 4-byte aligned (one float per lane covers columns 0..63).
+  struct BufArg {
+    const char* name;
+    const void* p;
+  };
+  Shape fused_shape_of(std::initializer_list<BufArg> bufs) const {
+    bool vec = vec_ok;
+    for (const BufArg& b : bufs) vec = vec && aligned16(b.p);
+    return pick_shape(dim, vec);
+  }
+  bool fused_shape_covers(std::initializer_list<BufArg> bufs) const {
+    Shape sh = fused_shape_of(bufs);
+    return dim <= uint32_t(sh.G * sh.VEC);
+  }
+  // ... or MHTE_INVALID_ARGUMENT, naming the buffer (as mhte_step_scatter / mhte_step_sum refuse it)
+  Shape fused_shape(const char* what, std::initializer_list<BufArg> bufs) const {
+    Shape sh = fused_shape_of(bufs);
+    if (dim > uint32_t(sh.G * sh.VEC)) {
+      std::string which;
+      for (const BufArg& b : bufs)
+        if (!aligned16(b.p)) which += std::string(which.empty() ? "" : ", ") + b.name;
+      throw Error(MHTE_INVALID_ARGUMENT,
+                  std::string(what) + ": rows of more than 64 floats must be 16-byte aligned (" + which +
+                      (which.empty() ? "row too wide for the fused step" : " is not") + "; table " + name +
+                      ", dim " + std::to_string(dim) + ")");
+    }
+    return sh;
   }
   bool basic_opts() const {   // SGD / Adagrad / FTRL only: the BASIC kernel instantiations
     for (uint32_t i = 0; i < nseg; ++i)
@@ -1131,7 +1163,7 @@ struct Table {
     a.global_step = 0;  // (the fused kernels take SGD / Adagrad / FTRL only)
     ++mut_epoch;
     ensure_capacity(uint64_t(n_max), st);
-    Shape sh = pick_shape(dim, vec_ok && aligned16(grads) && aligned16(grad_u));
+    Shape sh = fused_shape("sum_optimize", {{"grads", grads}, {"grad_unique", grad_u}});
     pending.reserve(size_t(n_max) + 1);
     // upper bound of the work items dd_finish may have queued (each heavy list has > kLightMax
     // entries and at most one partly filled chunk); surplus blocks exit on the device-side count
@@ -1167,7 +1199,7 @@ struct Table {
   void step_forward(const int64_t* ids, int64_t n, float* out, const RunView& nxt, DedupWs* ws_cur,
                     hipStream_t st) {
     if (n <= 0) throw Error(MHTE_INVALID_ARGUMENT, "step_forward: empty batch");
-    Shape sh = pick_shape(dim, vec_ok && aligned16(out));
+    Shape sh = fused_shape("step_forward", {{"embedding", out}});
     // (ws_cur: a round-1 form reserved the update's row handles in this launch; the build role's
     // table probe reserves them a launch earlier, off this launch's critical path — the argument is
     // accepted and ignored)
@@ -1179,7 +1211,11 @@ struct Table {
       sp.grad_u = pend_grad;
       sp.pending = pending.p;
       sp.a = pend_args;
-      if (pend_vec != sh.VEC) {  // (cannot happen for one table: same row shape both ways)
+      // the update stored the queued gradients for its own lane width, which follows the alignment of ITS
+      // buffers: a backward on a misaligned gradient (one float per lane) before a forward into an aligned
+      // embedding buffer (float4), or the other way round, lands here (rows of <= 64 floats; exercised by
+      // tests/test_alignment_forms_gpu.py) — the pass then runs on its own, in front of this launch
+      if (pend_vec != sh.VEC) {
         finish_pending(st);
         sp.enabled = 0;
       }
@@ -1287,7 +1323,7 @@ struct Table {
     ws.r_prealloc = false;
     // (prealloc: the rows were reserved — and their room made — when the batch was numbered)
     ensure_capacity(uint64_t(std::min<int64_t>(n_max, n)), st, prealloc ? kCapKeys : kCapBoth);
-    Shape sh = pick_shape(dim, vec_ok && aligned16(grads) && aligned16(grad_u));
+    Shape sh = fused_shape("step_backward", {{"grads", grads}, {"grad_unique", grad_u}});
     pending.reserve(size_t(n_max) + 1);
     const uint32_t cap_items = DedupWs::max_items(n);
     ws.part.reserve(size_t(cap_items) * dim + 16);
@@ -4062,7 +4098,10 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
       tk_record(t, tb, table, unique_ids, n_max, n_unique_dev, st);
       return;
     }
-    if (tb.fusable() && tb.basic_opts()) {   // (sum_apply_kernel is compiled for SGD / Adagrad / FTRL)
+    // (sum_apply_kernel is compiled for SGD / Adagrad / FTRL; a row of more than 64 floats in buffers that are
+    // not 16-byte aligned has no fused shape and takes the route of the wide rows below)
+    if (tb.fusable() && tb.basic_opts() &&
+        tb.fused_shape_covers({{"grads", grads}, {"grad_unique", grad_unique}})) {
       tb.sum_optimize(ws->ws, unique_ids, n_max, n_unique_dev, grads, list_start, list_end,
                       seg_pos, n, grad_unique, learning_rate, update_time,
                       (flags & MHTE_EXACT_ORDER) != 0, (flags & MHTE_DEFER_SLOWPATH) != 0, st);
@@ -4074,7 +4113,8 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
     // the ordered dedup: list_end == list_start + 1)
     if (list_end != list_start + 1)
       throw Error(MHTE_INVALID_ARGUMENT,
-                  "rows wider than 256 floats and optimizers beyond SGD / Adagrad / FTRL need the ordered "
+                  "rows wider than 256 floats, rows of more than 64 floats in buffers that are not 16-byte "
+                  "aligned and optimizers beyond SGD / Adagrad / FTRL need the ordered "
                   "mhte_unique (CSR occurrence lists) here; the pipelined step takes them as they are");
     mhte_status s2 = mhte_segment_sum(ws, grads, inverse, list_start, seg_pos, n_unique_dev, n,
                                       int32_t(tb.dim), grad_unique,
@@ -4202,6 +4242,9 @@ mhte_status mhte_table_step_forward(mhte_multi_table* t, int32_t table, const in
     HIP_OK(hipSetDevice(t->device));
     std::lock_guard<std::mutex> g(tb.mu);
     hps.locked();
+    // refused before anything changes: the next batch's run dedup is not begun, the displacement pass the
+    // previous update left stays queued
+    if (n > 0) tb.fused_shape("step_forward", {{"embedding", embedding}});
     hipStream_t st = S(stream);
     RunView nxt{};
     if (ws_next) {
@@ -4261,6 +4304,9 @@ mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, m
     if (!tb.fusable())
       throw Error(MHTE_INVALID_ARGUMENT, "step_backward: row too wide (or a whole-segment optimizer) "
                                          "for the fused step");
+    // refused before anything changes: no update time noted, the run dedup of the batch two ahead not begun,
+    // the queued displacement pass and the workspace's probe left as they are
+    tb.fused_shape("step_backward", {{"grads", grads}, {"grad_unique", grad_unique}});
     HIP_OK(hipSetDevice(t->device));
     tb.note_update_time(update_time);
     RunView ahead{};

@@ -105,7 +105,8 @@ class SparseStep:
     self.emb_u = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
     self.emb = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
     self.grad_u = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
-    lr0 = sum(table._slice_sizes[:self.idx])  # pylint: disable=protected-access
+    self._grad_stage = None     # aligned copy of a misaligned gradient of a wide row (backward)
+    lr0 =sum(table._slice_sizes[:self.idx])  # pylint: disable=protected-access
     self.lrs = np.ascontiguousarray(
         table.learning_rate[lr0:lr0 + table._slice_sizes[self.idx]])  # pylint: disable=protected-access
 
@@ -232,7 +233,17 @@ class SparseStep:
       self._joined = True
 
   def backward(self, grads: torch.Tensor, update_time: int, global_step: int = 0):
+    """Gradient sum + optimizer apply of the batch last given to ``forward``.  ``grads`` [batch, dim]
+    float32, contiguous.  The fused kernels move a row of more than 64 floats as float4s only, which
+    needs a 16-byte aligned base (the C entry points refuse anything else): a ``grads`` that is not —
+    a view at an odd float offset of a larger tensor — is copied into an aligned buffer of the step's
+    own first, allocated on first use ([batch, dim] floats)."""
     self._join()
+    if self.fusable and self.dim > 64 and grads.data_ptr() % 16:
+      if self._grad_stage is None:
+        self._grad_stage = torch.empty((self.batch, self.dim), dtype=torch.float32, device=self.emb.device)
+      self._grad_stage.copy_(grads.view(self.batch, self.dim))
+      grads = self._grad_stage
     if self._mode == "pipe":
       cur, nxt = self._cur, self._nxt
       ws_next = self._ws[nxt] if nxt is not None else None
