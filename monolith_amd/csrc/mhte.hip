@@ -23,6 +23,7 @@
 #include <future>
 #include <initializer_list>
 #include <thread>
+#include <type_traits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -305,6 +306,7 @@ static bool table_counters_alive(const void* p, uint64_t serial) {
 }
 
 // ------------------------------------------------------------------------------------------ dedup ws
+struct Table;
 struct DedupWs {
   int device = 0;
   DevBuf<int64_t> hkey;
@@ -349,16 +351,22 @@ struct DedupWs {
     return d;
   }
 
-  // scratch of the fused backward (sum_apply_kernel): block partial rows + zeroed arrival counters
-  void backward_scratch(int64_t n, uint32_t dim, uint32_t nblk_b, hipStream_t st) {
-    part.reserve(size_t(nblk_b) * 2 * dim + 16);
+  // the arrival counters of a batch of n positions: large enough and known to be zero (every kernel that
+  // counts arrivals leaves them zero again)
+  uint32_t* zeroed_arrive(size_t n, hipStream_t st) {
     const uint32_t* old = arrive.p;
-    arrive.reserve(size_t(n) + 2);
+    arrive.reserve(n + 2);
     if (arrive.p != old) arrive_clean = 0;
-    if (arrive_clean < size_t(n) + 2) {
+    if (arrive_clean < n + 2) {
       HIP_OK(hipMemsetAsync(arrive.p, 0, arrive.cap * sizeof(uint32_t), st));
       arrive_clean = arrive.cap;
     }
+    return arrive.p;
+  }
+  // scratch of the fused backward (sum_apply_kernel): block partial rows + zeroed arrival counters
+  void backward_scratch(int64_t n, uint32_t dim, uint32_t nblk_b, hipStream_t st) {
+    part.reserve(size_t(nblk_b) * 2 * dim + 16);
+    zeroed_arrive(size_t(n), st);
   }
 
   void unique(const int64_t* ids, int64_t n, int64_t* uids, uint32_t* inverse, uint32_t* seg_off,
@@ -405,13 +413,9 @@ struct DedupWs {
   DevBuf<uint16_t> r_seg;
   DevBuf<ItemHdr> r_item_hdr;
   DevBuf<uint32_t> r_cursor;   // shard packing cursors
-  bool r_prealloc = false;     // r_urec holds row reservations for the numbered batch
   DevBuf<URec> r_urec;         // ProbeOut of the numbered batch: per unique index, what the update
                                // needs in one load — incl. the row handle / slot of an id the table
                                // held when the batch was numbered, or a row reserved for it
-  bool r_hints = false;        // r_urec describes the numbered batch
-  Counters* r_res_ctr = nullptr;   // the table whose rows the records reserve ...
-  uint64_t r_res_serial = 0;       // ... and its serial number (register_counters)
   void probe_out_reserve(int64_t n) {
     const URec* old = r_urec.p;
     r_urec.reserve(size_t(n) + 1);
@@ -419,19 +423,52 @@ struct DedupWs {
     // memory must at least be well-formed)
     if (r_urec.p != old) HIP_OK(hipMemset(r_urec.p, 0, r_urec.cap * sizeof(URec)));
   }
-  // reservations of a numbered batch that is dropped instead of applied: the keys go back
-  void drop_reservations(hipStream_t st) {
-    if (r_prealloc && r_stage == 2 && r_res_ctr && table_counters_alive(r_res_ctr, r_res_serial))
-      // (the count is the workspace's own counter, ctr[0] — the user's n_unique buffer of the dropped batch
-      // may be gone by now)
-      rd_unreserve_kernel<<<32, 256, 0, st>>>(r_urec.p, rv.ctr, rv.n, r_res_ctr);
-    r_prealloc = false;
-    r_hints = false;
-    r_res_ctr = nullptr;
-  }
   uint32_t r_clean_cap = 0;  // run scratch [0, r_clean_cap] is all-empty
   int r_stage = 0;           // 0 idle, 1 dedup enqueued, 2 work list enqueued (ready for apply)
   RunView rv{};
+
+  // --- the probe of the numbered batch.  A probe (r_urec) belongs to ONE table, named by its counter
+  // block AND its serial number: for any other — another table, or the same one after a clear — it is
+  // void.  Its row reservations go back to that table when the batch is dropped instead of applied,
+  // unless the table went first.  r_stage and the four fields below are written by the transitions
+  // that follow and by begin_run_dedup / build_work_list, nowhere else.
+ private:
+  bool r_hints = false;            // r_urec describes the numbered batch
+  bool r_prealloc = false;         // ... and holds row reservations for it
+  Counters* r_res_ctr = nullptr;   // the table the probe is of ...
+  uint64_t r_res_serial = 0;       // ... and its serial number (register_counters)
+ public:
+  bool probed() const { return r_hints; }
+  bool holds_reservations() const { return r_prealloc && r_stage == 2 && r_res_ctr; }
+  inline bool probe_is_of(const Table& tb) const;
+  // the batch was numbered and probed against tb (reserved: with row reservations): ready for the apply
+  inline void adopt_probe(const Table& tb, bool reserved);
+  // a probe of another table, or of this one before it was cleared: its row handles and reservations
+  // mean nothing to the table about to be updated — forget them, in the heavy items' headers as well
+  void void_probe(hipStream_t st) {
+    r_hints = false;
+    r_prealloc = false;
+    r_res_ctr = nullptr;
+    HIP_OK(hipMemsetAsync(rv.ctr + 3, 0, sizeof(uint32_t), st));   // (its reservation count)
+    if (r_stage == 2) rd_items_unhint_kernel<<<8, 256, 0, st>>>(rv);
+  }
+  // the apply takes the probe: true if rows were reserved (and their room made) when it was taken
+  bool consume_probe() {
+    const bool prealloc = r_prealloc;
+    r_prealloc = false;
+    r_hints = false;
+    r_res_ctr = nullptr;
+    return prealloc;
+  }
+  void applied() { r_stage = 0; }   // the apply leaves the scratch all-empty
+  // reservations of a numbered batch that is dropped instead of applied: the keys go back
+  void drop_reservations(hipStream_t st) {
+    if (holds_reservations() && table_counters_alive(r_res_ctr, r_res_serial))
+      // (the count is the workspace's own counter, ctr[0] — the user's n_unique buffer of the dropped batch
+      // may be gone by now)
+      rd_unreserve_kernel<<<32, 256, 0, st>>>(r_urec.p, rv.ctr, rv.n, r_res_ctr);
+    (void)consume_probe();
+  }
 
   // items of a list of c occurrences < c / target + 1 (rd_item_blocks), lists > kLightMax
   static uint32_t max_items(int64_t n) {
@@ -537,34 +574,51 @@ static Shape pick_shape(uint32_t dim, bool vec_ok) {
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// A lane shape as compile-time constants: for_shape(sh, [&](auto g, auto v) { ... kernel<decltype(g)::value,
+// decltype(v)::value> ... }) runs the generic lambda's instance for sh — every launch that is compiled per
+// (G, VEC) selects its kernel here.  with_flag does the same for one run-time flag.
 // MHTE_DEV_FAST (development builds, scripts/dev_build.sh): only the dim-64 float4 shape is
 // instantiated, which cuts the compile from minutes to well under one; every other shape throws.
+template <int N>
+using Const = std::integral_constant<int, N>;
+template <class F>
+static inline void for_shape(Shape sh, F&& f) {
 #ifdef MHTE_DEV_FAST
-#define DISPATCH_G_VEC(shape, CALL)                                                            \
-  do {                                                                                         \
-    if ((shape).VEC == 4 && (shape).G == 16) { CALL(16, 4); }                                  \
-    else throw Error(MHTE_INTERNAL, "MHTE_DEV_FAST build: only G = 16, VEC = 4");         \
-  } while (0)
+  if (sh.VEC != 4 || sh.G != 16) throw Error(MHTE_INTERNAL, "MHTE_DEV_FAST build: only G = 16, VEC = 4");
+  f(Const<16>{}, Const<4>{});
 #else
-#define DISPATCH_G_VEC(shape, CALL)                                  \
-  do {                                                               \
-    if ((shape).VEC == 4) {                                          \
-      switch ((shape).G) {                                           \
-        case 8: { CALL(8, 4); } break;                               \
-        case 16: { CALL(16, 4); } break;                             \
-        case 32: { CALL(32, 4); } break;                             \
-        default: { CALL(64, 4); } break;                             \
-      }                                                              \
-    } else {                                                         \
-      switch ((shape).G) {                                           \
-        case 8: { CALL(8, 1); } break;                               \
-        case 16: { CALL(16, 1); } break;                             \
-        case 32: { CALL(32, 1); } break;                             \
-        default: { CALL(64, 1); } break;                             \
-      }                                                              \
-    }                                                                \
-  } while (0)
+  auto for_g = [&](auto v) {
+    switch (sh.G) {
+      case 8: f(Const<8>{}, v); break;
+      case 16: f(Const<16>{}, v); break;
+      case 32: f(Const<32>{}, v); break;
+      default: f(Const<64>{}, v); break;
+    }
+  };
+  if (sh.VEC == 4) for_g(Const<4>{});
+  else for_g(Const<1>{});
 #endif
+}
+template <class F>
+static inline auto with_flag(bool on, F&& f) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// MHTE_EXACT_ORDER in the step kernels (single-table and multi-table step alike): lists of <= kStepLightMax
+// occurrences are summed in occurrence order by the id-major groups in every mode; the heavy ones get their
+// strictly sequential sums from a launch in front of the update (`pre`: a workgroup streams a list's rows
+// through LDS, one wavefront adds them in order) and the item workgroups only apply them.  `walk`: round 5's
+// form, one lane group walking each list — rows wider than 256 floats, or MHTE_EXACT_WALK=1 (A/B; 4.8 ms per
+// step at Zipf(1.2)).
+struct ExactMode {
+  bool pre, walk;
+  uint32_t light_max() const { return walk ? 0xffffffffu : uint32_t(kStepLightMax); }
+};
+static ExactMode exact_mode(bool exact_order, uint32_t dim) {
+  static const bool force_walk = getenv("MHTE_EXACT_WALK") != nullptr && atoi(getenv("MHTE_EXACT_WALK")) != 0;
+  const bool pre = exact_order && !force_walk && dim <= 256u;
+  return ExactMode{pre, exact_order && !pre};
+}
 
 // ------------------------------------------------------------------------------------------ clock
 // seconds on a monotonic clock (+ the test hook's offset): the eviction cadence
@@ -1001,16 +1055,12 @@ struct Table {
       const uint32_t g = uint32_t((groups * sh.G + 511) / 512);
       TableView v = view;
       v.trace = trace_region(kTagLookup, g, 512);
-#define LK(G_)                                                                                   \
-  LAUNCH_HOT(kTagLookup, (lookup_kernel_u<G_, 4, 2, 1, 512>), g, 512, st, v, ids, n, n_dev, out, \
-             count_hits ? 1 : 0)
-      switch (sh.G) {
-        case 8: LK(8); break;
-        case 16: LK(16); break;
-        case 32: LK(32); break;
-        default: LK(64); break;
-      }
-#undef LK
+      for_shape(sh, [&](auto g_, auto v_) {
+        constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+        if constexpr (V == 4)   // (the float4 form only)
+          LAUNCH_HOT(kTagLookup, (lookup_kernel_u<G, 4, 2, 1, 512>), g, 512, st, v, ids, n, n_dev, out,
+                     count_hits ? 1 : 0);
+      });
       HIP_OK(hipGetLastError());
       return;
     }
@@ -1018,10 +1068,10 @@ struct Table {
     const dim3 grid(uint32_t((threads + 255) / 256));
     TableView v = view;
     v.trace = trace_region(kTagLookup, grid.x, 256);
-#define CALL(G_, V_) \
-  LAUNCH_HOT(kTagLookup, (lookup_kernel<G_, V_>), grid, 256, st, v, ids, n, n_dev, out, count_hits ? 1 : 0)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+      LAUNCH_HOT(kTagLookup, (lookup_kernel<G, V>), grid, 256, st, v, ids, n, n_dev, out, count_hits ? 1 : 0);
+    });
     HIP_OK(hipGetLastError());
   }
 
@@ -1030,6 +1080,23 @@ struct Table {
   template <int OP>
   static auto slowpath_fn(int vec) {
     return vec == 4 ? slowpath_kernel<4, OP> : slowpath_kernel<1, OP>;
+  }
+
+  // ... and the fast path's: the whole-segment optimizer's instance only where the table has one
+  template <int G, int V, int OP>
+  static auto upsert_instance(bool has_group_opt) {
+    return (OP == kOpOptimize && has_group_opt) ? upsert_kernel<G, V, OP, true> : upsert_kernel<G, V, OP>;
+  }
+  // the arguments every update path hands its kernels; a null lrs: zero rates
+  ApplyArgs apply_args(const float* lrs, int64_t update_time, int64_t global_step, int sum_dups,
+                       int filter_mode) const {
+    ApplyArgs a;
+    for (int i = 0; i < kMaxSegments; ++i) a.lr[i] = (lrs && i < int(nseg)) ? lrs[i] : 0.f;
+    a.ts = static_cast<uint32_t>(update_time);
+    a.sum_dups = sum_dups;
+    a.filter_mode = filter_mode;
+    a.global_step = global_step;
+    return a;
   }
 
   template <int OP>
@@ -1047,18 +1114,11 @@ struct Table {
     const int64_t threads = n * sh.G;
     const dim3 grid(uint32_t((threads + 255) / 256));
     uint32_t* pend = pending.p;
-#define CALL(G_, V_)                                                                               \
-  do {                                                                                             \
-    if (OP == kOpOptimize && has_group_opt) {                                                      \
-      LAUNCH_HOT(kTagUpsert, (upsert_kernel<G_, V_, OP, true>), grid, 256, st, view, ids, n, n_dev, \
-                 values, seg_off, seg_pos, a, status, pend, skp);                                  \
-    } else {                                                                                       \
-      LAUNCH_HOT(kTagUpsert, (upsert_kernel<G_, V_, OP>), grid, 256, st, view, ids, n, n_dev,      \
-                 values, seg_off, seg_pos, a, status, pend, skp);                                  \
-    }                                                                                              \
-  } while (0)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+      LAUNCH_HOT(kTagUpsert, (upsert_instance<G, V, OP>(has_group_opt)), grid, 256, st, view, ids, n, n_dev,
+                 values, seg_off, seg_pos, a, status, pend, skp);
+    });
     slowpath_fn<OP>(sh.VEC)<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
     if (a.filter_mode) filter_maintain(st, uint64_t(n));
     HIP_OK(hipGetLastError());
@@ -1071,14 +1131,10 @@ struct Table {
     finish_pending(st);
     if (n <= 0) return;
     if (n > (int64_t(1) << 31) - 4096) throw Error(MHTE_INVALID_ARGUMENT, "too many ids in one op");
-    ApplyArgs a;
-    for (int i = 0; i < kMaxSegments; ++i) a.lr[i] = (lrs && i < int(nseg)) ? lrs[i] : 0.f;
-    a.ts = static_cast<uint32_t>(update_time);
-    a.sum_dups = (flags & MHTE_SUM_DUPLICATES) ? 1 : 0;
-    a.global_step = t_global_step;
     // admission filter (tf_bridge.cc): Assign / Optimize are guarded by Contains; the multi-table
     // AssignAdd goes through AssignAdd2, which is not (:230-232); Reinitialize never filters
-    a.filter_mode = (OP == kOpReinit) ? 0 : (OP == kOpAssignAdd ? 3 : 1);
+    const ApplyArgs a = apply_args(lrs, update_time, t_global_step, (flags & MHTE_SUM_DUPLICATES) ? 1 : 0,
+                                   (OP == kOpReinit) ? 0 : (OP == kOpAssignAdd ? 3 : 1));
     ensure_capacity(uint64_t(n), st);
     if (flags & MHTE_IDS_UNIQUE) {
       launch_upsert<OP>(ids, n, n_dev, values, nullptr, nullptr, a, status, st);
@@ -1155,12 +1211,7 @@ struct Table {
     if (n != ws.last_n)
       throw Error(MHTE_FAILED_PRECONDITION,
                   "sum_optimize: workspace does not hold the occurrence lists of this batch");
-    ApplyArgs a;
-    for (int i = 0; i < kMaxSegments; ++i) a.lr[i] = (lrs && i < int(nseg)) ? lrs[i] : 0.f;
-    a.ts = static_cast<uint32_t>(update_time);
-    a.sum_dups = 1;
-    a.filter_mode = 1;
-    a.global_step = 0;  // (the fused kernels take SGD / Adagrad / FTRL only)
+    const ApplyArgs a = apply_args(lrs, update_time, 0, 1, 1);  // (global_step: SGD / Adagrad / FTRL only here)
     ++mut_epoch;
     ensure_capacity(uint64_t(n_max), st);
     Shape sh = fused_shape("sum_optimize", {{"grads", grads}, {"grad_unique", grad_u}});
@@ -1175,18 +1226,14 @@ struct Table {
     uint32_t* pend = pending.p;
     TableView v = view;
     v.trace = trace_region(kTagSumApply, nblk_a + nblk_b, 256);
-#define CALL(G_, V_)                                                                              \
-  LAUNCH_HOT(kTagSumApply, (sum_apply_kernel<G_, V_>), nblk_a + nblk_b, 256, st,                  \
-             v, uids, n_dev, n_max, grads, lst_start, lst_end, seg_pos, ws.work.p,             \
-             ws.heavy_n.p + 3, nblk_b, light_max, ws.part.p, ws.arrive.p, grad_u, a, pend)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+      LAUNCH_HOT(kTagSumApply, (sum_apply_kernel<G, V>), nblk_a + nblk_b, 256, st, v, uids, n_dev, n_max, grads,
+                 lst_start, lst_end, seg_pos, ws.work.p, ws.heavy_n.p + 3, nblk_b, light_max, ws.part.p,
+                 ws.arrive.p, grad_u, a, pend);
+    });
     HIP_OK(hipGetLastError());
-    pend_valid = true;
-    pend_uids = uids;
-    pend_grad = grad_u;
-    pend_args = a;
-    pend_vec = sh.VEC;
+    queued.queue(uids, grad_u, a, sh.VEC);
     filter_maintain(st, uint64_t(n_max));
     if (!defer_slowpath) finish_pending(st);
   }
@@ -1195,31 +1242,48 @@ struct Table {
   //   step_forward   lookup of this batch | run dedup of the next batch
   //                  | displacement pass of the previous update (gated, usually idle)
   //   step_backward  apply of this batch | heavy work list of the next batch
-  // ws_cur: unused (kept for the C entry point's signature)
-  void step_forward(const int64_t* ids, int64_t n, float* out, const RunView& nxt, DedupWs* ws_cur,
-                    hipStream_t st) {
+  // the instances of the two launches for a lane shape (BASIC: SGD / Adagrad / FTRL only)
+  template <int G, int V>
+  static auto step_fwd_instance(int unr, bool basic) {
+    if (unr == 2) return basic ? step_fwd_kernel<G, V, 2, true> : step_fwd_kernel<G, V, 2, false>;
+    return basic ? step_fwd_kernel<G, V, 3, true> : step_fwd_kernel<G, V, 3, false>;
+  }
+  // filt: a table with an admission filter takes the instances that consult it (FILT; the others carry no
+  // filter code — with it the headline instance kept 11 spilled registers, without it 2).  optk >= 0: the
+  // instance compiled for that optimizer alone (one-segment FULL tables with float4 lanes, no filter:
+  // 61 -> 7-17 spilled registers for Adam, and the row fetched ahead as the BASIC instances do).
+  template <int G, int V>
+  static auto step_bwd_instance(bool basic, bool oneseg, bool filt, int optk) {
+    if (filt) {
+      if (oneseg) return basic ? step_bwd_kernel<G, V, true, false, -1, true> : step_bwd_kernel<G, V, true, true, -1, true>;
+      return basic ? step_bwd_kernel<G, V, false, false, -1, true> : step_bwd_kernel<G, V, false, true, -1, true>;
+    }
+    if constexpr (V == 4) {
+      switch (optk) {
+        case kOptMomentum: return step_bwd_kernel<G, 4, true, true, kOptMomentum>;
+        case kOptAdadelta: return step_bwd_kernel<G, 4, true, true, kOptAdadelta>;
+        case kOptRmsprop: return step_bwd_kernel<G, 4, true, true, kOptRmsprop>;
+        case kOptRmspropV2: return step_bwd_kernel<G, 4, true, true, kOptRmspropV2>;
+        case kOptAdam: return step_bwd_kernel<G, 4, true, true, kOptAdam>;
+        case kOptAmsgrad: return step_bwd_kernel<G, 4, true, true, kOptAmsgrad>;
+        default: break;
+      }
+    }
+    if (oneseg) return basic ? step_bwd_kernel<G, V, true> : step_bwd_kernel<G, V, true, true>;
+    return basic ? step_bwd_kernel<G, V, false> : step_bwd_kernel<G, V, false, true>;
+  }
+
+  void step_forward(const int64_t* ids, int64_t n, float* out, const RunView& nxt, hipStream_t st) {
     if (n <= 0) throw Error(MHTE_INVALID_ARGUMENT, "step_forward: empty batch");
     Shape sh = fused_shape("step_forward", {{"embedding", out}});
-    // (ws_cur: a round-1 form reserved the update's row handles in this launch; the build role's
-    // table probe reserves them a launch earlier, off this launch's critical path — the argument is
-    // accepted and ignored)
-    (void)ws_cur;
+    const PendingPass pp = take_pending(sh.VEC, st);
     SlowArgs sp{};
-    sp.enabled = pend_valid ? 1 : 0;
-    if (pend_valid) {
-      sp.uids = pend_uids;
-      sp.grad_u = pend_grad;
+    sp.enabled = pp.valid ? 1 : 0;
+    if (pp.valid) {
+      sp.uids = pp.uids;
+      sp.grad_u = pp.grad;
       sp.pending = pending.p;
-      sp.a = pend_args;
-      // the update stored the queued gradients for its own lane width, which follows the alignment of ITS
-      // buffers: a backward on a misaligned gradient (one float per lane) before a forward into an aligned
-      // embedding buffer (float4), or the other way round, lands here (rows of <= 64 floats; exercised by
-      // tests/test_alignment_forms_gpu.py) — the pass then runs on its own, in front of this launch
-      if (pend_vec != sh.VEC) {
-        finish_pending(st);
-        sp.enabled = 0;
-      }
-      pend_valid = false;
+      sp.a = pp.args;
     }
     // every workgroup of the launch resident at once (two 1024-thread workgroups per CU); the lookup
     // role covers its groups in grid-stride trips
@@ -1243,24 +1307,11 @@ struct Table {
     TableView v = view;
     v.trace = trace_region(kTagStepFwd, grid.x, kRdBlock);
     const bool basic = basic_opts();   // (the displacement role's update code)
-#define CALLU(G_, V_, U_)                                                                        \
-  do {                                                                                           \
-    if (basic) {                                                                                 \
-      LAUNCH_HOT(kTagStepFwd, (step_fwd_kernel<G_, V_, U_, true>), grid, kRdBlock, st, nxt, v, ids, n, out, \
-                 count_hits ? 1 : 0, sp, nblk_l);                                                \
-    } else {                                                                                     \
-      LAUNCH_HOT(kTagStepFwd, (step_fwd_kernel<G_, V_, U_, false>), grid, kRdBlock, st, nxt, v, ids, n, out, \
-                 count_hits ? 1 : 0, sp, nblk_l);                                                \
-    }                                                                                            \
-  } while (0)
-#define CALL(G_, V_)                              \
-  do {                                            \
-    if (unr == 2) { CALLU(G_, V_, 2); }           \
-    else { CALLU(G_, V_, 3); }                    \
-  } while (0)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
-#undef CALLU
+    for_shape(sh, [&](auto g_, auto v_) {
+      constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+      LAUNCH_HOT(kTagStepFwd, (step_fwd_instance<G, V>(unr, basic)), grid, kRdBlock, st, nxt, v, ids, n, out,
+                 count_hits ? 1 : 0, sp, nblk_l);
+    });
     HIP_OK(hipGetLastError());
   }
 
@@ -1272,94 +1323,59 @@ struct Table {
                      int64_t global_step = 0, const RunView& ahead = RunView{}) {
     finish_pending(st);
     if (n <= 0 || n_max <= 0) throw Error(MHTE_INVALID_ARGUMENT, "step_backward: empty batch");
-    // MHTE_EXACT_ORDER: lists of <= kStepLightMax occurrences are summed in occurrence order by the id-major
-    // groups in every mode; the heavy ones get their strictly sequential sums from a launch in front of the
-    // update (rd_exact_sum_kernel: a workgroup streams a list's rows through LDS, one wavefront adds them in
-    // order) and the item workgroups only apply them.  MHTE_EXACT_WALK=1: round 5's form, one lane group
-    // walking each list (A/B; 4.8 ms per step at Zipf(1.2)).
-    static const bool exact_walk = getenv("MHTE_EXACT_WALK") != nullptr && atoi(getenv("MHTE_EXACT_WALK")) != 0;
-    const bool exact_pre = exact_order && !exact_walk && dim <= 256u;
-    const bool exact_old = exact_order && !exact_pre;
+    const ExactMode exact = exact_mode(exact_order, dim);
     if (ws.r_stage == 0 || int64_t(ws.rv.n) != n || ws.rv.uids != uids || ws.rv.n_unique != n_dev)
       throw Error(MHTE_FAILED_PRECONDITION,
                   "step_backward: workspace does not hold the run dedup of this batch");
-    // a probe of another table, or of this one before it was cleared (a restore between two steps):
-    // its row handles and reservations mean nothing here — probe again
-    if (ws.r_hints && (ws.r_res_ctr != view.ctr || ws.r_res_serial != ctr_serial)) {
-      ws.r_hints = false;
-      ws.r_prealloc = false;
-      ws.r_res_ctr = nullptr;
-      HIP_OK(hipMemsetAsync(ws.rv.ctr + 3, 0, sizeof(uint32_t), st));   // (its reservation count)
-      if (ws.r_stage == 2) rd_items_unhint_kernel<<<8, 256, 0, st>>>(ws.rv);
-    }
+    // a probe of another table, or of this one before it was cleared (a restore between two steps): probe again
+    if (ws.probed() && !ws.probe_is_of(*this)) ws.void_probe(st);
     // first step of a pipeline (later ones were numbered — and probed — a step ahead, inside the
     // previous update's launch)
-    if (ws.r_stage == 1 || !ws.r_hints) {
-      // (r_stage 2 without hints: numbered on its own, mhte_step_dedup — the probe alone)
+    if (ws.r_stage == 1 || !ws.probed()) {
+      // (r_stage 2 without a probe: numbered on its own, mhte_step_dedup — the probe alone)
       ws.probe_out_reserve(n);
-      const bool reserve = flt_slots == nullptr && !ws.r_prealloc;
+      const bool reserve = flt_slots == nullptr;
       if (reserve) ensure_capacity(uint64_t(std::min<int64_t>(n_max, n)), st, kCapRows);
       ProbeOut po{ws.r_urec.p, reserve ? 1u : 0u};
       if (ws.r_stage == 1)
         rd_build_probe_kernel<<<DedupWs::build_blocks(ws.rv), 256, 0, st>>>(ws.rv, uint32_t(kStepLightMax), view, po);
       else
         rd_probe_kernel<<<uint32_t(std::min<int64_t>(256, (n + 255) / 256)), 256, 0, st>>>(
-            ws.rv, view, po, uint32_t(n), exact_old ? 0xffffffffu : uint32_t(kStepLightMax));
+            ws.rv, view, po, uint32_t(n), exact.light_max());
       HIP_OK(hipGetLastError());
-      ws.r_stage = 2;
-      ws.r_hints = true;
-      ws.r_res_ctr = view.ctr;
-      ws.r_res_serial = ctr_serial;
-      if (reserve) ws.r_prealloc = true;
+      ws.adopt_probe(*this, reserve);
     }
-    ApplyArgs a;
-    for (int i = 0; i < kMaxSegments; ++i) a.lr[i] = (lrs && i < int(nseg)) ? lrs[i] : 0.f;
-    a.ts = static_cast<uint32_t>(update_time);
-    a.sum_dups = 1;
-    a.filter_mode = 1;
-    a.global_step = global_step;  // (batch softmax)
+    const ApplyArgs a = apply_args(lrs, update_time, global_step /* batch softmax */, 1, 1);
     ++mut_epoch;
-    const bool prealloc = ws.r_prealloc;  // (rows reserved — and room ensured — by step_forward)
-    ws.r_prealloc = false;
     // (prealloc: the rows were reserved — and their room made — when the batch was numbered)
+    const bool prealloc = ws.consume_probe();
     ensure_capacity(uint64_t(std::min<int64_t>(n_max, n)), st, prealloc ? kCapKeys : kCapBoth);
     Shape sh = fused_shape("step_backward", {{"grads", grads}, {"grad_unique", grad_u}});
     pending.reserve(size_t(n_max) + 1);
     const uint32_t cap_items = DedupWs::max_items(n);
     ws.part.reserve(size_t(cap_items) * dim + 16);
-    {
-      const uint32_t* old = ws.arrive.p;
-      ws.arrive.reserve(size_t(n) + 2);
-      if (ws.arrive.p != old) ws.arrive_clean = 0;
-      if (ws.arrive_clean < size_t(n) + 2) {
-        HIP_OK(hipMemsetAsync(ws.arrive.p, 0, ws.arrive.cap * sizeof(uint32_t), st));
-        ws.arrive_clean = ws.arrive.cap;
-      }
-    }
     ApplyCtl c{};
     c.grads = grads;
     c.grad_u = grad_u;
     c.pending = pending.p;
     c.part = ws.part.p;
-    c.arrive = ws.arrive.p;
+    c.arrive = ws.zeroed_arrive(size_t(n), st);
     c.n_max = n_max;
-    c.light_max = exact_old ? 0xffffffffu : uint32_t(kStepLightMax);
-    c.pre_summed = exact_pre ? 1u : 0u;
+    c.light_max = exact.light_max();
+    c.pre_summed = exact.pre ? 1u : 0u;
     c.urow = nullptr;
     c.uloc = nullptr;
     c.uts = nullptr;
     c.urec = ws.r_urec.p;
     c.trusted = 0;   // (an update, a displacement pass, a doubling may lie between probe and use: the
                      // kernel checks every hint against the slot's key)
-    ws.r_hints = false;
-    ws.r_res_ctr = nullptr;
     // fixed grids with grid-stride loops: item workgroups first (longest chain), sized for the
     // work a Zipf batch has; more ids / items than workgroups just means more trips
     const uint32_t groups_per_wg = uint32_t(256 / sh.G);
     // residency budget: 4 workgroups of 256 threads per CU (launch bounds of step_bwd_kernel)
     const uint32_t slots = uint32_t(kBwdBlocksPerCu * num_cus);
-    c.nblk_items = exact_old ? 0u : std::min<uint32_t>(cap_items, uint32_t(num_cus) * 10 / 8);
-    if (exact_pre) {
+    c.nblk_items = exact.walk ? 0u : std::min<uint32_t>(cap_items, uint32_t(num_cus) * 10 / 8);
+    if (exact.pre) {
       const uint32_t gx = std::min<uint32_t>(cap_items, uint32_t(num_cus));
       if (sh.VEC == 4) rd_exact_sum_kernel<4><<<gx, kExactThreads, 0, st>>>(ws.rv, grads, dim, ws.part.p);
       else rd_exact_sum_kernel<1><<<gx, kExactThreads, 0, st>>>(ws.rv, grads, dim, ws.part.p);
@@ -1403,62 +1419,18 @@ struct Table {
     TableView v = view;
     v.trace = trace_region(kTagStepBwd, grid.x, 256);
     const RunView cur = ws.rv;
-    const bool basic = basic_opts();
-    // one-segment tables of Momentum / Adadelta / RMSProp / Adam / AMSGrad rows with float4 lanes: the
-    // instance compiled for that optimizer alone (step_bwd_kernel<.., OPTK>: 61 -> 7-17 spilled registers for
-    // Adam, and the row fetched ahead as the SGD / Adagrad / FTRL instances do)
+    const bool basic = basic_opts(), oneseg = nseg == 1, filt = flt_slots != nullptr;
     static const bool no_optk = getenv("MHTE_NO_OPTK") != nullptr;   // (A/B: the one FULL instance for all)
-    // a table with an admission filter: the instances that consult it (FILT; the others carry no filter code —
-    // with it the headline instance kept 11 spilled registers, without it 2)
-    const bool filt = flt_slots != nullptr;
     const int optk =
-        (!basic && nseg == 1 && sh.VEC == 4 && !view.seg[0].sr16 && !no_optk && !filt) ? int(view.seg[0].opt) : -1;
-#define CALL_FILT(G_, V_, S_, F_)                                                                                \
-  LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, V_, S_, F_, -1, true>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da)
-#define CALL_OPTK(G_, K_)                                                                                     \
-  LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, 4, true, true, K_>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da)
-#define CALL(G_, V_) \
-  do {                                                                                               \
-    if (filt) {                                                                                      \
-      if (basic && nseg == 1) CALL_FILT(G_, V_, true, false);                                        \
-      else if (basic) CALL_FILT(G_, V_, false, false);                                               \
-      else if (nseg == 1) CALL_FILT(G_, V_, true, true);                                             \
-      else CALL_FILT(G_, V_, false, true);                                                           \
-    } else if (V_ == 4 && optk == kOptMomentum) {                                                    \
-      CALL_OPTK(G_, kOptMomentum);                                                                   \
-    } else if (V_ == 4 && optk == kOptAdadelta) {                                                    \
-      CALL_OPTK(G_, kOptAdadelta);                                                                   \
-    } else if (V_ == 4 && optk == kOptRmsprop) {                                                     \
-      CALL_OPTK(G_, kOptRmsprop);                                                                    \
-    } else if (V_ == 4 && optk == kOptRmspropV2) {                                                   \
-      CALL_OPTK(G_, kOptRmspropV2);                                                                  \
-    } else if (V_ == 4 && optk == kOptAdam) {                                                        \
-      CALL_OPTK(G_, kOptAdam);                                                                       \
-    } else if (V_ == 4 && optk == kOptAmsgrad) {                                                     \
-      CALL_OPTK(G_, kOptAmsgrad);                                                                    \
-    } else if (!basic && nseg == 1) {                                                                \
-      LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, V_, true, true>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da); \
-    } else if (!basic) {                                                                             \
-      LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, V_, false, true>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da); \
-    } else if (nseg == 1) {                                                                          \
-      LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, V_, true>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da);  \
-    } else {                                                                                         \
-      LAUNCH_HOT(kTagStepBwd, (step_bwd_kernel<G_, V_, false>), grid, 256, st, nxt, nblk_build, v, cur, c, a, po, da); \
-    }                                                                                                \
-  } while (0)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
-#undef CALL_OPTK
-#undef CALL_FILT
+        (!basic && oneseg && sh.VEC == 4 && !view.seg[0].sr16 && !no_optk && !filt) ? int(view.seg[0].opt) : -1;
+    for_shape(sh, [&](auto g_, auto v_) {
+      constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+      LAUNCH_HOT(kTagStepBwd, (step_bwd_instance<G, V>(basic, oneseg, filt, optk)), grid, 256, st, nxt, nblk_build,
+                 v, cur, c, a, po, da);
+    });
     hipError_t le = hipGetLastError();
-    ws.r_stage = 0;  // the apply leaves the scratch all-empty
-    if (nblk_build) {
-      ws_next->r_stage = 2;
-      ws_next->r_hints = true;
-      ws_next->r_prealloc = reserve_next;
-      ws_next->r_res_ctr = view.ctr;
-      ws_next->r_res_serial = ctr_serial;
-    }
+    ws.applied();
+    if (nblk_build) ws_next->adopt_probe(*this, reserve_next);
     if (le != hipSuccess) {
       ws.r_clean_cap = 0;
       if (ws_next) ws_next->r_clean_cap = 0;
@@ -1467,20 +1439,42 @@ struct Table {
     filter_maintain(st, uint64_t(n));
     // the displacement pass rides in the next step_forward (or runs on its own if anything else
     // touches the table first)
-    pend_valid = true;
-    pend_uids = uids;
-    pend_grad = grad_u;
-    pend_args = a;
-    pend_vec = sh.VEC;
+    queued.queue(uids, grad_u, a, sh.VEC);
   }
 
-  // displacement pass for the ids the last fused backward could not place (both buckets full);
-  // a no-op kernel when there are none, which is the usual case
-  bool pend_valid = false;
-  const int64_t* pend_uids = nullptr;
-  const float* pend_grad = nullptr;
-  ApplyArgs pend_args{};
-  int pend_vec = 4;
+  // The displacement pass for the ids the last fused backward could not place (both buckets full; a no-op
+  // kernel when there are none, which is the usual case).  The update queues it; the next step_forward
+  // takes it into its own launch, and whatever else touches the table first runs it on its own
+  // (finish_pending).
+  struct PendingPass {
+    bool valid = false;
+    const int64_t* uids = nullptr;
+    const float* grad = nullptr;
+    ApplyArgs args{};
+    int vec = 4;   // lane width the update stored the queued gradients for
+    void queue(const int64_t* uids_, const float* grad_, const ApplyArgs& args_, int vec_) {
+      valid = true;
+      uids = uids_;
+      grad = grad_;
+      args = args_;
+      vec = vec_;
+    }
+    PendingPass take() {
+      const PendingPass p = *this;
+      valid = false;
+      return p;
+    }
+  };
+  PendingPass queued;
+  // ... taken by a launch of lane width `vec`.  The update stored the queued gradients for its own lane width,
+  // which follows the alignment of ITS buffers: a backward on a misaligned gradient (one float per lane) before
+  // a forward into an aligned embedding buffer (float4), or the other way round (rows of <= 64 floats;
+  // exercised by tests/test_alignment_forms_gpu.py) — a forward with another lane width runs the pass on its
+  // own first, in front of its launch, and carries none.
+  PendingPass take_pending(int vec, hipStream_t st) {
+    if (queued.valid && queued.vec != vec) finish_pending(st);
+    return queued.take();
+  }
   // a displacement pass somebody else owes this table (the id-sharded step runs the pass of its last owner
   // update inside its NEXT owner lookup's launch, mhte_shard_host.h): whoever touches the table first — any
   // op, a save, a doubling — makes it happen now
@@ -1491,11 +1485,11 @@ struct Table {
       void (*f)(void*, hipStream_t) = ext_flush;
       f(ext_ctx, st);   // (clears the hook of every table it covers)
     }
-    if (!pend_valid) return;
-    pend_valid = false;
+    if (!queued.valid) return;
+    const PendingPass pp = queued.take();
     ++mut_epoch;
-    LAUNCH_HOT(kTagSlowpath, slowpath_fn<kOpOptimize>(pend_vec), 1, 64, st, view, pend_uids, pend_grad,
-               nullptr, nullptr, pend_args, nullptr, pending.p, nullptr);
+    LAUNCH_HOT(kTagSlowpath, slowpath_fn<kOpOptimize>(pp.vec), 1, 64, st, view, pp.uids, pp.grad,
+               nullptr, nullptr, pp.args, nullptr, pending.p, nullptr);
     HIP_OK(hipGetLastError());
   }
 
@@ -1540,6 +1534,17 @@ struct Table {
     HIP_OK(hipGetLastError());
   }
 };
+
+inline bool DedupWs::probe_is_of(const Table& tb) const {
+  return r_res_ctr == tb.view.ctr && r_res_serial == tb.ctr_serial;
+}
+inline void DedupWs::adopt_probe(const Table& tb, bool reserved) {
+  r_stage = 2;
+  r_hints = true;
+  r_prealloc = reserved;
+  r_res_ctr = tb.view.ctr;
+  r_res_serial = tb.ctr_serial;
+}
 
 // ------------------------------------------------------------------------------------------ multi table
 }  // namespace mhte
@@ -3928,7 +3933,7 @@ mhte_status mhte_dedup_ws_create(int32_t device, mhte_dedup_ws** out) {
   });
 }
 void mhte_dedup_ws_destroy(mhte_dedup_ws* ws) {
-  if (ws && ws->ws.r_prealloc && ws->ws.r_stage == 2 && ws->ws.r_res_ctr) {
+  if (ws && ws->ws.holds_reservations()) {
     // a numbered batch that was never applied: its row reservations' keys go back to the table
     // (the table may already be gone: its counters then are freed memory — only while it lives)
     // (the numbering / probe that wrote the records ran on the caller's stream, which the null stream
@@ -3983,9 +3988,9 @@ mhte_status mhte_gather_rows(const float* src, const uint32_t* index, int64_t n,
     Shape sh = pick_shape(uint32_t(dim), dim % 4 == 0 && aligned16(src) && aligned16(out));
     const dim3 grid(uint32_t((n * sh.G + 255) / 256));
     hipStream_t st = S(stream);
-#define CALL(G_, V_) gather_rows_kernel<G_, V_><<<grid, 256, 0, st>>>(src, index, n, uint32_t(dim), out)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      gather_rows_kernel<decltype(g_)::value, decltype(v_)::value><<<grid, 256, 0, st>>>(src, index, n, uint32_t(dim), out);
+    });
     HIP_OK(hipGetLastError());
   });
 }
@@ -4003,10 +4008,10 @@ mhte_status mhte_segment_sum(mhte_dedup_ws* ws, const float* grads, const uint32
     Shape sh = pick_shape(uint32_t(dim), dim % 4 == 0 && aligned16(grads) && aligned16(out));
     if (exact_order) {
       const dim3 grid(uint32_t((n * sh.G + 255) / 256));
-#define CALL(G_, V_) \
-  segsum_exact_kernel<G_, V_><<<grid, 256, 0, st>>>(grads, n_unique_dev, seg_off, seg_pos, uint32_t(dim), out)
-      DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+      for_shape(sh, [&](auto g_, auto v_) {
+        segsum_exact_kernel<decltype(g_)::value, decltype(v_)::value><<<grid, 256, 0, st>>>(
+            grads, n_unique_dev, seg_off, seg_pos, uint32_t(dim), out);
+      });
     } else {
       const int win = sh.G < 16 ? sh.G : 16;
       const int64_t nwin = (n + win - 1) / win;
@@ -4015,12 +4020,12 @@ mhte_status mhte_segment_sum(mhte_dedup_ws* ws, const float* grads, const uint32
       float* part = ws->ws.part.p;
       uint32_t* last_u = ws->ws.last_u.p;
       const dim3 grid(uint32_t((nwin * sh.G + 255) / 256));
-#define CALL(G_, V_)                                                                         \
-  segsum_window_kernel<G_, V_><<<grid, 256, 0, st>>>(grads, inverse, seg_off, seg_pos, uint32_t(n), \
-                                                     uint32_t(dim), out, part, last_u);      \
-  segsum_combine_kernel<G_, V_><<<dim3(uint32_t(nwin)), 256, 0, st>>>(seg_off, last_u, uint32_t(dim), out, part)
-      DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+      for_shape(sh, [&](auto g_, auto v_) {
+        constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+        segsum_window_kernel<G, V><<<grid, 256, 0, st>>>(grads, inverse, seg_off, seg_pos, uint32_t(n),
+                                                         uint32_t(dim), out, part, last_u);
+        segsum_combine_kernel<G, V><<<dim3(uint32_t(nwin)), 256, 0, st>>>(seg_off, last_u, uint32_t(dim), out, part);
+      });
     }
     HIP_OK(hipGetLastError());
   });
@@ -4086,12 +4091,7 @@ mhte_status mhte_table_sum_optimize_n(mhte_multi_table* t, int32_t table, mhte_d
                                            "(CSR occurrence lists)");
       tb.finish_pending(st);
       if (n <= 0 || n_max <= 0) return;
-      ApplyArgs a;
-      for (int i = 0; i < kMaxSegments; ++i) a.lr[i] = i < int(tb.nseg) ? learning_rate[i] : 0.f;
-      a.ts = static_cast<uint32_t>(update_time);
-      a.sum_dups = 1;
-      a.filter_mode = 1;
-      a.global_step = global_step;
+      const ApplyArgs a = tb.apply_args(learning_rate, update_time, global_step, 1, 1);
       tb.ensure_capacity(uint64_t(n_max), st);
       tb.launch_upsert<kOpOptimize>(unique_ids, n_max, n_unique_dev, grads, list_start, seg_pos, a, nullptr, st);
       tb.maybe_evict(st);
@@ -4166,24 +4166,17 @@ static void step_gather(DedupWs& ws, const float* in, const uint32_t* index, int
   c.dim = uint32_t(dim);
   if (!SCATTER) {
     ws.part.reserve(size_t(cap_items) * dim + 16);
-    const uint32_t* old = ws.arrive.p;
-    ws.arrive.reserve(size_t(n) + 2);
-    if (ws.arrive.p != old) ws.arrive_clean = 0;
-    if (ws.arrive_clean < size_t(n) + 2) {
-      HIP_OK(hipMemsetAsync(ws.arrive.p, 0, ws.arrive.cap * sizeof(uint32_t), st));
-      ws.arrive_clean = ws.arrive.cap;
-    }
     c.part = ws.part.p;
-    c.arrive = ws.arrive.p;
+    c.arrive = ws.zeroed_arrive(size_t(n), st);
   }
   const uint32_t groups_per_wg = uint32_t(256 / sh.G);
   c.nblk_items = std::min<uint32_t>(cap_items, 288);
   c.nblk_ids = std::max<uint32_t>(1, std::min<uint32_t>(uint32_t((n + groups_per_wg - 1) / groups_per_wg), 1024));
   const dim3 grid(c.nblk_items + c.nblk_ids);
   const RunView d = ws.rv;
-#define CALL(G_, V_) rd_gather_kernel<G_, V_, SCATTER><<<grid, 256, 0, st>>>(d, c)
-  DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+  for_shape(sh, [&](auto g_, auto v_) {
+    rd_gather_kernel<decltype(g_)::value, decltype(v_)::value, SCATTER><<<grid, 256, 0, st>>>(d, c);
+  });
   HIP_OK(hipGetLastError());
 }
 }  // namespace mhte
@@ -4254,7 +4247,7 @@ mhte_status mhte_table_step_forward(mhte_multi_table* t, int32_t table, const in
     }
     if (ws_cur && ws_cur == ws_next)
       throw Error(MHTE_INVALID_ARGUMENT, "step_forward: ws_cur must differ from ws_next");
-    tb.step_forward(id, n, embedding, nxt, ws_cur ? &ws_cur->ws : nullptr, st);
+    tb.step_forward(id, n, embedding, nxt, st);
   });
 }
 
@@ -4364,12 +4357,10 @@ mhte_status mhte_fill_with_offset_map(const int64_t* pos, int64_t n, const float
                                              aligned16(value_buffer));
     const dim3 grid(uint32_t((n * sh.G + 255) / 256));
     hipStream_t st = S(stream);
-#define CALL(G_, V_)                                                                          \
-  scatter_offsets_kernel<G_, V_><<<grid, 256, 0, st>>>(pos, n, value, value_offset_map,       \
-                                                       value_offset_map_split, uint32_t(dim), \
-                                                       value_buffer)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      scatter_offsets_kernel<decltype(g_)::value, decltype(v_)::value><<<grid, 256, 0, st>>>(
+          pos, n, value, value_offset_map, value_offset_map_split, uint32_t(dim), value_buffer);
+    });
     HIP_OK(hipGetLastError());
   });
 }
@@ -4386,12 +4377,10 @@ mhte_status mhte_fill_with_offset_map_gradient(const int64_t* pos, int64_t n, co
                                              aligned16(backprop_grad));
     const dim3 grid(uint32_t((n * sh.G + 255) / 256));
     hipStream_t st = S(stream);
-#define CALL(G_, V_)                                                                        \
-  gather_sum_offsets_kernel<G_, V_><<<grid, 256, 0, st>>>(pos, n, grad, grad_offset_map,    \
-                                                          grad_offset_map_split,            \
-                                                          uint32_t(dim), backprop_grad)
-    DISPATCH_G_VEC(sh, CALL);
-#undef CALL
+    for_shape(sh, [&](auto g_, auto v_) {
+      gather_sum_offsets_kernel<decltype(g_)::value, decltype(v_)::value><<<grid, 256, 0, st>>>(
+          pos, n, grad, grad_offset_map, grad_offset_map_split, uint32_t(dim), backprop_grad);
+    });
     HIP_OK(hipGetLastError());
   });
 }

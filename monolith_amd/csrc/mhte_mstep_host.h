@@ -418,6 +418,22 @@ struct MultiStep {
     }
   }
 
+  // the backward launch's instance for an optimizer family (full: beyond SGD / Adagrad / FTRL), a lane width,
+  // one-segment tables, and the admission filter's code
+  using BwdKernel = void (*)(MBwdArgs);
+  static BwdKernel mstep_bwd_instance(bool full, int width, bool oneseg, bool filt) {
+    return with_flag(full, [&](auto f_) {
+      return with_flag(width == 4, [&](auto w4_) {
+        return with_flag(oneseg, [&](auto o_) {
+          return with_flag(filt, [&](auto fl_) -> BwdKernel {
+            return mstep_bwd_kernel<decltype(f_)::value, decltype(w4_)::value ? 4 : 1, decltype(o_)::value,
+                                    decltype(fl_)::value>;
+          });
+        });
+      });
+    });
+  }
+
   struct BwdPlan {
     int64_t global_step = 0;
     const float* grads = nullptr;
@@ -461,27 +477,20 @@ struct MultiStep {
           any_apply = true;
           bt.grad_off = uint32_t(grad_off);
           grad_off += int64_t(n) * tb.dim;
-          for (int i = 0; i < kMaxSegments; ++i)
-            bt.a.lr[i] = (i < int(tb.nseg)) ? p.lrs[lr_off + i] : 0.f;
-          bt.a.ts = static_cast<uint32_t>(p.update_time);
-          bt.a.sum_dups = 1;
-          bt.a.filter_mode = 1;
-          bt.a.global_step = p.global_step;
+          bt.a = tb.apply_args(p.lrs + lr_off, p.update_time, p.global_step, 1, 1);
           // MHTE_EXACT_ORDER: the heavy lists' sums come from mstep_exact_sum_kernel, launched in front (as in the
-          // single-table step; MHTE_EXACT_WALK=1: round 5's form, every list walked by its lane group)
-          static const bool exact_walk = getenv("MHTE_EXACT_WALK") != nullptr && atoi(getenv("MHTE_EXACT_WALK")) != 0;
-          const bool exact_pre = p.exact_order && !exact_walk && tb.dim <= 256u;
-          const bool exact_old = p.exact_order && !exact_pre;
-          if (exact_pre) {
+          // single-table step, exact_mode)
+          const ExactMode exact = exact_mode(p.exact_order, tb.dim);
+          if (exact.pre) {
             bt.apply |= 2u;
             any_exact = true;
           }
-          bt.light_max = exact_old ? 0xffffffffu : uint32_t(kStepLightMax);
+          bt.light_max = exact.light_max();
           bt.hints = (has_hints[slot_cur] && fwd_epoch[slot_cur][t] == tb.mut_epoch) ? 1u : 0u;
           bt.gv = shape_code(tb, uint64_t(bt.grad_off));
           const uint32_t groups_per_wg = 256u / shape_lanes(bt.gv);
           const uint32_t cap_items = DedupWs::max_items(n);
-          bt.nblk_items = exact_old ? 0u
+          bt.nblk_items = exact.walk ? 0u
                                     : std::min<uint32_t>(cap_items, std::min<uint32_t>(
                                               uint32_t(num_cus) * 10 / 8, std::max<uint32_t>(8, share / 4)));
           const uint32_t need = (n + groups_per_wg - 1) / groups_per_wg;
@@ -510,20 +519,12 @@ struct MultiStep {
       // ... and the instances with the admission filter's code only when a table of the launch has a filter
       bool filt = false;
       for (uint32_t k = 0; k < tc; ++k) filt = filt || mt->tables[t0 + k]->flt_slots != nullptr;
-#define MHTE_BWD_LAUNCH(F_, W_, O_)                                                                              \
-  if (fam[F_][W_ == 1][O_]) {                                                                                    \
-    if (filt) LAUNCH_HOT(kTagMStepBwd, (mstep_bwd_kernel<F_ != 0, W_, O_ != 0, true>), dim3(gx, tc), 256, st, A); \
-    else LAUNCH_HOT(kTagMStepBwd, (mstep_bwd_kernel<F_ != 0, W_, O_ != 0, false>), dim3(gx, tc), 256, st, A);   \
-  }
-      MHTE_BWD_LAUNCH(0, 4, 1);
-      MHTE_BWD_LAUNCH(0, 4, 0);
-      MHTE_BWD_LAUNCH(0, 1, 1);
-      MHTE_BWD_LAUNCH(0, 1, 0);
-      MHTE_BWD_LAUNCH(1, 4, 1);
-      MHTE_BWD_LAUNCH(1, 4, 0);
-      MHTE_BWD_LAUNCH(1, 1, 1);
-      MHTE_BWD_LAUNCH(1, 1, 0);
-#undef MHTE_BWD_LAUNCH
+      for (int full = 0; full < 2; ++full)
+        for (int w1 = 0; w1 < 2; ++w1)
+          for (int oneseg = 1; oneseg >= 0; --oneseg)
+            if (fam[full][w1][oneseg])
+              LAUNCH_HOT(kTagMStepBwd, mstep_bwd_instance(full != 0, w1 ? 1 : 4, oneseg != 0, filt), dim3(gx, tc), 256,
+                         st, A);
       HIP_OK(hipGetLastError());
       if (any_apply) {
         mstep_slow_kernel<<<tc, 64 * kSlowWaves, 0, st>>>(A);
@@ -804,14 +805,8 @@ static void fused_optimize_segments(mhte_multi_table* t, const int64_t* ids,
         A.g[k] = uint8_t(seg_shape_code(tb, worst));
       }
       A.pending[k] = tb.pending.p;
-      ApplyArgs& a = A.a[k];
-      for (int i = 0; i < kMaxSegments; ++i)
-        a.lr[i] = (i < int(tb.nseg)) ? learning_rates[lr_off + i] : 0.f;
+      A.a[k] = tb.apply_args(learning_rates + lr_off, req_time, global_step, 0, 0);
       lr_off += tb.nseg;  // (restarts per shard in the reference: the same slice for every shard)
-      a.ts = static_cast<uint32_t>(req_time);
-      a.sum_dups = 0;
-      a.filter_mode = 0;
-      a.global_step = global_step;
     }
     for (int y = 0; y < ns; ++y) {
       const uint32_t n = uint32_t(fused_slot_size[s0 + y]);

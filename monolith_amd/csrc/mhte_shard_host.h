@@ -1148,6 +1148,26 @@ struct ShardStep {
     ids_hdr_sent[slot_next] = false;
   }
 
+  // the owner-side instances.  Lookup: a lane width, with the owed displacement pass folded in or not.
+  // Apply: a lane width, the whole-segment optimizer (GROUP), more than one rank (MULTI) and the fast loop of
+  // SGD / Adagrad / FTRL tables (FAST; never together with GROUP).
+  using OwnerKernel = void (*)(ShardOwnerArgs);
+  static OwnerKernel shard_lookup_instance(int width, bool fold) {
+    if (width == 4) return fold ? shard_lookup_kernel<4, true, 2> : shard_lookup_kernel<4, false, 2>;
+    return fold ? shard_lookup_kernel<1, true, 2> : shard_lookup_kernel<1, false, 2>;
+  }
+  static OwnerKernel shard_apply_instance(int width, bool group, bool multi, bool fast) {
+    if (group && fast) throw Error(MHTE_INTERNAL, "shard_apply: no fast instance for a whole-segment optimizer");
+    return with_flag(width == 4, [&](auto w4_) {
+      return with_flag(multi, [&](auto m_) -> OwnerKernel {
+        constexpr int W = decltype(w4_)::value ? 4 : 1;
+        constexpr bool M = decltype(m_)::value;
+        if (group) return shard_apply_kernel<W, true, M, false>;
+        return fast ? shard_apply_kernel<W, false, M, true> : shard_apply_kernel<W, false, M, false>;
+      });
+    });
+  }
+
   // arguments of the owner-side launches for tables [t0, t0 + tc)
   void owner_args(ShardOwnerArgs& A, int slot, bool apply, uint32_t t0, uint32_t tc) const {
     A.views = ConstViews(mt->d_views.p);
@@ -1218,15 +1238,11 @@ struct ShardStep {
       for (uint32_t i = 0; i < tc; ++i) ((A.g[i] & 1u) ? w1 : w4) = true;
       if (fold) gx = std::max(gx, tc);
       const dim3 grid(gx, uint32_t(world) * tc + (fold ? 1u : 0u));
-#define MHTE_LOOKUP_LAUNCH(W_)                                                                      \
-  do {                                                                                              \
-    if (fold) LAUNCH_HOT(kTagShardLookup, (shard_lookup_kernel<W_, true, 2>), grid, 512, st, A);    \
-    else LAUNCH_HOT(kTagShardLookup, (shard_lookup_kernel<W_, false, 2>), grid, 512, st, A);        \
-  } while (0)
-      if (w4) MHTE_LOOKUP_LAUNCH(4);
-      if (w1) MHTE_LOOKUP_LAUNCH(1);
-#undef MHTE_LOOKUP_LAUNCH
-      launches += (w4 ? 1u : 0u) + (w1 ? 1u : 0u);
+      for (int w : {4, 1})
+        if (w == 4 ? w4 : w1) {
+          LAUNCH_HOT(kTagShardLookup, shard_lookup_instance(w, fold), grid, 512, st, A);
+          ++launches;
+        }
       HIP_OK(hipGetLastError());
     }
     if (fold) {
@@ -1266,13 +1282,9 @@ struct ShardStep {
       for (uint32_t i = 0; i < k.tc; ++i) {
         Table& tb = *mt->tables[t0 + i];
         A.pending[i] = tb.pending.p;
-        ApplyArgs& a = A.a[i];
-        for (int j = 0; j < kMaxSegments; ++j) a.lr[j] = (j < int(tb.nseg)) ? lrs[lr_off + j] : 0.f;
+        // (filter_mode: an owner asks its filter about every id it does not hold)
+        A.a[i] = tb.apply_args(lrs + lr_off, update_time, global_step, 0, tb.flt_slots ? 1 : 0);
         lr_off += tb.nseg;
-        a.ts = static_cast<uint32_t>(update_time);
-        a.sum_dups = 0;
-        a.filter_mode = tb.flt_slots ? 1 : 0;   // an owner asks its filter about every id it does not hold
-        a.global_step = global_step;
         gx = std::max(gx, (sized_n(t0 + i) + 256u / shape_lanes(A.g[i]) - 1) / (256u / shape_lanes(A.g[i])));
         k.inst[A.g[i] & 1u][(A.g[i] >> 1) & 1u] = true;
         k.inst3[A.g[i] & 1u][(A.g[i] >> 1) & 1u][A.fast[i] ? 1 : 0] = true;
@@ -1300,21 +1312,14 @@ struct ShardStep {
           if (own_slot == slot && own_epoch[t0 + i] == mt->tables[t0 + i]->mut_epoch) A.x.hints |= 1u << i;
         const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>(k.gx, std::max<uint32_t>(8, k.gx_fill / uint32_t(world))));
         const dim3 grid(gx, uint32_t(world) * k.tc);
-#define MHTE_APPLY_LAUNCH(W_, G_, F_)                                                                          \
-  do {                                                                                                       \
-    if (k.inst3[W_ == 1][G_][F_]) {                                                                          \
-      if (world > 1) LAUNCH_HOT(kTagShardUpsert, (shard_apply_kernel<W_, G_ != 0, true, F_ != 0>), grid, 256, st, A);  \
-      else LAUNCH_HOT(kTagShardUpsert, (shard_apply_kernel<W_, G_ != 0, false, F_ != 0>), grid, 256, st, A);           \
-      ++launches;                                                                                            \
-    }                                                                                                        \
-  } while (0)
-        MHTE_APPLY_LAUNCH(4, 0, 1);
-        MHTE_APPLY_LAUNCH(1, 0, 1);
-        MHTE_APPLY_LAUNCH(4, 0, 0);
-        MHTE_APPLY_LAUNCH(1, 0, 0);
-        MHTE_APPLY_LAUNCH(4, 1, 0);
-        MHTE_APPLY_LAUNCH(1, 1, 0);
-#undef MHTE_APPLY_LAUNCH
+        // (the fast instances first, the whole-segment optimizer's last; float4 before one float per lane)
+        static const struct { bool group, fast; } kinds[] = {{false, true}, {false, false}, {true, false}};
+        for (const auto& kd : kinds)
+          for (int w : {4, 1})
+            if (k.inst3[w == 1][kd.group][kd.fast]) {
+              LAUNCH_HOT(kTagShardUpsert, shard_apply_instance(w, kd.group, world > 1, kd.fast), grid, 256, st, A);
+              ++launches;
+            }
         HIP_OK(hipGetLastError());
       }
       x_dirty = false;

@@ -1986,3 +1986,54 @@ def test_clear_between_numbering_and_update_voids_the_probe(exact):
   np.testing.assert_array_equal(got[np.isin(probe, fill) & ~np.isin(probe, b[1])],
                                 exp[np.isin(probe, fill) & ~np.isin(probe, b[1])])   # untouched rows: exact
   assert mt.size("emb") == probe.size == ot.size()
+
+
+@pytest.mark.parametrize("dim", [8, 68])
+def test_probe_taken_for_one_table_is_void_for_another(dim):
+  """A workspace numbered and probed inside table A's update (DedupWs::adopt_probe: hints for the ids A
+  holds, rows reserved in A for the others) and then applied to table B: the probe names A's counter block
+  and serial, so B's update forgets it (void_probe) and probes again — with A's row handles it would write
+  into rows that B has given to other ids.  B against the oracle, bit for bit; A keeps its own rows and, once
+  the workspace is gone, its key count.  The batch: two dedup workgroups, one list of more than 512
+  occurrences (several work items) beside light lists; dim 68 is the 32-lane float4 shape."""
+  n, lr = 2048, 0.01
+  rng = np.random.default_rng(1000 + dim)
+  universe = np.arange(1, 65, dtype=np.int64) * 104729 + (1 << 33)
+  y = universe[rng.integers(1, 64, n)]
+  y[rng.permutation(n)[:600]] = universe[0]
+  assert (y == universe[0]).sum() == 600 and np.unique(y).size > 32
+  # A's own batch holds half of those ids (hints) and lacks the rest (reservations)
+  x = np.concatenate([universe[rng.integers(0, 32, n // 2)], S.id_batch(77, n // 2, 10**6, "uniform")])
+  # B holds every third of them, behind rows that A never handed out in that order
+  fill = np.concatenate([np.arange(1, 301, dtype=np.int64) * 7919 + (1 << 40), universe[1::3]])
+  vals = rng.standard_normal((fill.size, dim)).astype(np.float32)
+  mta, mtb = make({"emb": adagrad_cfg(dim, lr, 0.1)}), make({"emb": adagrad_cfg(dim, lr, 0.1)})
+  ota, otb = (O.Table(O.segment(dim, O.OPT_ADAGRAD, p=(0.1, 0.0)), 1) for _ in range(2))
+  mtb.assign({"emb": (ids_t(fill), val_t(vals))}, req_time=5)
+  otb.assign(fill, vals, 5)
+  ws = [D.DedupWorkspace() for _ in range(2)]
+  uids = [torch.empty(n, dtype=torch.int64, device="cuda") for _ in range(2)]
+  nu = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(2)]
+  emb = torch.empty((n, dim), dtype=torch.float32, device="cuda")
+  grad_u = torch.empty((n, dim), dtype=torch.float32, device="cuda")
+  lrs = np.asarray([lr], dtype=np.float32)
+  xd, yd = ids_t(x), ids_t(y)
+  gx, gy = S.grad_batch(0, n, dim), S.grad_batch(1, n, dim)
+  ws[0].step_dedup(xd, uids[0], nu[0])
+  mta.table_step_forward(0, xd, emb, ws[1], yd, uids[1], nu[1])
+  mta.table_step_backward(0, ws[0], ws[1], uids[0], nu[0], val_t(gx), grad_u, lrs, S.update_time(0),
+                          exact_order=True)   # y: numbered and probed against A, rows reserved in A
+  _oracle_step(ota, x, gx, dim, lr, S.update_time(0))
+  mtb.table_step_forward(0, yd, emb)
+  np.testing.assert_array_equal(emb.cpu().numpy(), otb.lookup(y)[0])
+  mtb.table_step_backward(0, ws[1], None, uids[1], nu[1], val_t(gy), grad_u, lrs, S.update_time(1),
+                          exact_order=True)
+  _oracle_step(otb, y, gy, dim, lr, S.update_time(1))
+  probe = np.unique(np.concatenate([fill, y]))
+  np.testing.assert_array_equal(mtb.lookup({"emb": ids_t(probe)})["emb"].cpu().numpy(), otb.lookup(probe)[0])
+  assert mtb.size("emb") == probe.size == otb.size()
+  seen = np.unique(x)
+  np.testing.assert_array_equal(mta.lookup({"emb": ids_t(seen)})["emb"].cpu().numpy(), ota.lookup(seen)[0])
+  for w in ws:
+    w.close()
+  assert mta.size("emb") == seen.size == ota.size()
