@@ -400,6 +400,37 @@ def test_optimizer_restatement_bit_exact_vs_compiled_reference(case):
 
 
 @needs_ref_opt
+@pytest.mark.parametrize("dim", [64, 100, 260])
+@pytest.mark.parametrize("case", [c for c in REF_OPT_CASES if c[1] == O.OPT_GROUP_ADAGRAD], ids=lambda c: c[0])
+def test_group_adagrad_restatement_vs_compiled_reference_at_wide_segments(case, dim):
+  """GroupAdaGrad is the one optimizer whose step reads the whole segment (the largest squared gradient, the
+  norm of the intermediate vector as ONE chain in element order): the oracle's restatement against the
+  reference's own object at the segment widths the GPU tests of tests/test_optimizer_shapes_gpu.py use —
+  64, 100 and 260 floats, where the device walks more than one trip of its lane group.  The first call's
+  gradient is small enough for ||z|| < l2 (the branch that zeroes the segment: weights exactly zero although
+  the gradient is not); the later ones take the shrinking branch."""
+  name, opt, p = case
+  rng = np.random.Generator(np.random.PCG64(dim))
+  t = O.Table([O.segment(dim, opt, p=p)], 1)
+  r = O.RefOptimizer(opt, dim, p)
+  one = np.array([7], np.int64)
+  shrunk = 0
+  for step in range(25):
+    scale = 1e-5 if step == 0 else 10.0 ** rng.integers(-3, 2)
+    g = (rng.standard_normal(dim) * scale).astype(np.float32)
+    lr = float(np.float32(10.0 ** rng.uniform(-3, -0.5)))
+    t.optimize(one, g[None, :], [lr], 0)
+    num_ref, ctx_ref = r.optimize(g, lr)
+    num, ctx = _oracle_row(t, dim)
+    assert np.array_equal(num.view(np.uint32), num_ref.view(np.uint32)), (name, dim, step)
+    assert np.array_equal(ctx.view(np.uint32)[:ctx_ref.size], ctx_ref.view(np.uint32)), (name, dim, step)
+    if step == 0:
+      assert g.any() and not num_ref.any(), (name, dim)
+    shrunk += int(num_ref.all())
+  assert shrunk > 0, (name, dim)
+
+
+@needs_ref_opt
 def test_reference_as_built_avx_fma_flavour_stays_within_the_parity_bar():
   """The reference as its .bazelrc builds it (-mavx2 -mfma: avx_utils.h's vector Adagrad, contracted
   multiply-adds elsewhere) against the scalar arithmetic the engine follows: within north_star's
