@@ -447,7 +447,14 @@ mhte_status mhte_fused_reduce_and_split_grad(const int32_t* row_splits, const in
  * flags: MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS — the caller states that every feature instance has exactly
  * one fid and no embedding row is referenced twice (the per-occurrence rows of a lookup feeding a
  * one-id-per-feature model): slices on float4 boundaries then move as float4 copies and the gradient
- * is a plain store instead of a float atomic per element. */
+ * is a plain store instead of a float atomic per element.  The host checks what it can see: widths,
+ * strides and pointers that are not float4-aligned take the general kernels, and a gradient call in
+ * which two slices of the same feature_idx overlap in [start, start + dim) — the same columns of one
+ * feature fed to two layouts — is a sum of two addends per element, so it takes the form it would
+ * take without the flag (grouped sums, or float atomics under MHTE_POOL_ATOMICS=1); the forward is
+ * unaffected.  What lives on the device stays the caller's promise: one fid per instance, distinct
+ * rows, and no shared feature list (nfl_offset bit 31) whose row receives a gradient from more than
+ * one batch row. */
 enum { MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS = 1 };
 typedef struct {
   int32_t feature_idx, start, dim;

@@ -4600,7 +4600,25 @@ static void layout_launch(bool forward, const float* const* embeddings, const in
     return t;
   };
   // ---- the gradient without float atomics (general form; MHTE_POOL_ATOMICS=1 keeps the atomic one)
+  // The flag's plain stores hold only while no element of a feature's row is named by two slices (the
+  // same columns of one feature in a CONCAT and in a STACK layout, say): there the gradient is a sum of
+  // two addends, and the call takes the form it would take without the flag.  The forward only reads.
   bool copy_form = (flags & MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS) != 0 && n_fid == n_feature;
+  if (!forward && copy_form) {
+    std::vector<std::pair<int32_t, int32_t>> order;   // (feature, slice) by feature, then start
+    order.reserve(size_t(n_slices));
+    for (int32_t i = 0; i < n_slices; ++i) order.emplace_back(slices[i].feature_idx, i);
+    std::sort(order.begin(), order.end(), [&](const std::pair<int32_t, int32_t>& a, const std::pair<int32_t, int32_t>& b) {
+      return a.first != b.first ? a.first < b.first : slices[a.second].start < slices[b.second].start;
+    });
+    int64_t end = 0;   // one past the last column a slice of the current feature has named so far
+    for (size_t i = 0; copy_form && i < order.size(); ++i) {
+      const mhte_layout_slice& sc = slices[order[i].second];
+      if (i == 0 || order[i].first != order[i - 1].first) end = INT64_MIN;
+      if (int64_t(sc.start) < end) copy_form = false;
+      end = std::max(end, int64_t(sc.start) + std::max(sc.dim, 0));
+    }
+  }
   if (!forward && !copy_form && !pool_atomics() && n_fid > 0) {
     std::vector<LayoutTask> tasks(static_cast<size_t>(n_slices));
     std::vector<uint32_t> t_off(size_t(n_nfl) + 1, 0), t_idx;
@@ -4698,6 +4716,20 @@ static void layout_launch(bool forward, const float* const* embeddings, const in
         while (k + span < n_slices && slices[k + span].out_type == 2 &&
                slices[k + span].out_index == slices[k].out_index) ++span;
       const bool cont = addn_open;
+      // (forward) a slice that writes floats an earlier slice of this launch writes too starts the next
+      // launch: launches run in stream order, so the later slice's values stay, as in the op's own loop
+      // (inside one launch the two stores come from different lanes or workgroups, in no order)
+      bool clash = false;
+      for (int32_t q = 0; forward && !clash && q < nt; ++q) {
+        const LayoutTask& t = A.task[q];
+        const mhte_layout_slice& sc = slices[k];
+        if (t.out_index != sc.out_index) continue;
+        const int64_t w0 = int64_t(t.dim) * (t.pooling == kPoolFirstN ? std::max(1, t.max_seq) : 1),
+                      w1 = int64_t(sc.dim) * (sc.pooling == kPoolFirstN ? std::max(1, sc.max_sequence_length) : 1);
+        clash = t.out_stride != sc.out_row_floats ||
+                (int64_t(sc.out_offset) < t.out_offset + w0 && int64_t(t.out_offset) < sc.out_offset + w1);
+      }
+      if (clash) break;
       if (span > kMaxLayoutTasks) {
         if (nt > 0) break;             // (a long ADDN layout starts its own launch)
         span = kMaxLayoutTasks;
@@ -4728,13 +4760,17 @@ static void layout_launch(bool forward, const float* const* embeddings, const in
         ++nu;
         ++nt;
       }
-      A.zero_missing = 1;
+      // (one bit per output; whole rows are decided without pointer tables only: at most kMaxLayoutOut outputs)
+      uint32_t mask = 0;
+      for (size_t o = 0; o < out_written.size() && o < 32; ++o)
+        if (out_written[o]) mask |= 1u << o;
+      A.zero_missing = int32_t(mask);
     }
     A.n_units = nu;
     const dim3 grid(uint32_t((int64_t(batch) * 16 + 255) / 256), uint32_t(nu));
     // one fid per feature instance (asserted by the caller), copies of float4-aligned slices: the
     // vector copy form, plain stores for the gradient
-    bool fast = (flags & MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS) != 0 && n_fid == n_feature;
+    bool fast = copy_form;
     for (int32_t q = 0; fast && q < nt; ++q) {
       const LayoutTask& t = A.task[q];
       fast = t.pooling != kPoolFirstN && ((t.start | t.dim | t.out_offset | t.out_stride) & 3) == 0 &&

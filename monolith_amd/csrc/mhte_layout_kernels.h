@@ -49,8 +49,9 @@ struct LayoutArgs {
   const int32_t* feature_offset;
   const uint32_t* nfl_offset;
   int32_t n_fid, n_feature, n_nfl, batch, n_emb, n_units;
-  int32_t zero_missing;   // layout_rows_kernel<true>: a (slice, row) without a fid is written as zeros (the
-                          // output was not zero-filled beforehand: the launch writes every column of it)
+  int32_t zero_missing;   // layout_rows_kernel<true>, bit o: a (slice, row) of output o without a fid is written
+                          // as zeros (that output was not zero-filled beforehand: the launch writes every column
+                          // of it; an output behind the fill keeps what an earlier, overlapping slice wrote)
   // when the model has more matrices / outputs than the inline arrays hold: the same four tables in
   // device memory (x_emb != nullptr), uploaded by the host for the call
   const float* const* x_emb;
@@ -127,7 +128,8 @@ __device__ __forceinline__ bool layout_fid_range(const LayoutArgs& A, int32_t nf
 // Fast form for the common shape of a recommendation batch after a per-occurrence lookup: every
 // feature instance has exactly ONE fid, SUM / MEAN pooling (a copy), every slice boundary, row
 // stride and output offset a multiple of 4 floats, and (gradient) no embedding row referenced twice
-// — the host checks what it can and the caller asserts the rest (MHTE_LAYOUT_UNIQUE_ROWS).  A lane
+// — the host checks what it can (alignment; gradient: no two slices of one feature overlapping in
+// [start, start + dim)) and the caller asserts the rest (MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS).  A lane
 // moves float4s; the gradient is a plain store instead of a float atomic per element.
 template <bool FORWARD>
 __global__ __launch_bounds__(256) void layout_copy_kernel(LayoutArgs A) {
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(256) void layout_rows_kernel(LayoutArgs A) {
           src = reinterpret_cast<unsigned long long>(layout_emb(A, i1) + uint64_t(i2) * layout_stride(A, i1) +
                                                      uint32_t(t.start));
       }
-      if (!src && FORWARD && A.zero_missing) src = 1ull;
+      if (!src && FORWARD && ((uint32_t(A.zero_missing) >> (uint32_t(t.out_index) & 31u)) & 1u)) src = 1ull;
     }
     s_src[p] = src;
     s_dst[p] = dst;

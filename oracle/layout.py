@@ -7,6 +7,9 @@ Checkers of fused_embedding_to_layout (csrc/mhte_layout_kernels.h):
         fused_embedding_to_layout.cc:1037-1225: walks the op's OWN inputs (fid_offset,
         feature_offset, nfl_offset with the shared bit).
 
+  layout_model_slices   the forward over raw slices (the C ABI's mhte_layout_slice records) instead of a
+        configuration: for slices no configuration produces (gaps, overlaps, rows beyond the batch).
+
   reference_forward_case / reference_grad_case   the reference's own tests restated: the input
         generation AND the truth procedure of native_training/fused_embedding_to_layout_test.py
         :176-530 (forward: 199 feature slots over two tables, SHARED lists for even slots, SUM / MEAN /
@@ -338,20 +341,71 @@ def layout_model(embs, fid_offset, feature_offset, nfl_offset, batch, cfgs):
   for t_idx, sc, oc, i, off, b, rows in _walk(fid_offset, feature_offset, nfl_offset, batch, cfgs):
     fc = cfgs.feature_configs[sc.feature_name]
     view = _view(outs[t_idx], oc, i, off, sc.end - sc.start, b)
+    valid = [(i1, i2) for (i1, i2) in rows if i1 < len(embs)]   # (a matrix index past the list: skipped, :226)
     if fc.pooling_type == FIRSTN:
-      for s_, (i1, i2) in enumerate(rows[:fc.max_sequence_length]):
+      for s_, (i1, i2) in enumerate(valid[:fc.max_sequence_length]):
         view[s_, :] = embs[i1][i2, sc.start:sc.end]
       continue
     acc = None
-    for (i1, i2) in rows:
+    for (i1, i2) in valid:
       x = embs[i1][i2, sc.start:sc.end]
       if fc.pooling_type == MEAN:
         x = x / np.float32(len(rows))
       acc = x.copy() if acc is None else acc + x
+    if acc is None:
+      acc = np.zeros(sc.end - sc.start, np.float32)
     if oc.out_type == ADDN:
       view += acc
     else:
       view[:] = acc
+  return outs
+
+
+def layout_model_slices(embs, fid_offset, feature_offset, nfl_offset, batch, slices, out_lens):
+  """The forward over RAW slices — records with the fields of the C ABI's mhte_layout_slice
+  (feature_idx, start, dim, pooling, max_sequence_length, out_type, out_index, out_offset,
+  out_row_floats), in call order — instead of a configuration: gather, pool, place at out_offset of
+  row b of output out_index; every other float of an output (out_lens floats each, rows beyond the
+  batch included) is zero.  Slices are walked in order, so where two of them name the same output
+  floats the later one's values stay; consecutive ADDN slices of one output are one sum.
+  -> flat float32 arrays"""
+  outs = [np.zeros(int(n), np.float32) for n in out_lens]
+  n_feature, n_fid, n_nfl = len(feature_offset), len(fid_offset), len(nfl_offset)
+  for sc in slices:
+    nfl = int(sc.feature_idx)
+    if nfl < 0 or nfl >= n_nfl:
+      continue
+    enc = int(nfl_offset[nfl])
+    shared, noff = enc >> 31, enc & 0x7fffffff
+    nxt = (int(nfl_offset[nfl + 1]) & 0x7fffffff) if nfl < n_nfl - 1 else n_feature
+    if nxt - noff <= 0:
+      continue
+    start, dim, stride = int(sc.start), int(sc.dim), int(sc.out_row_floats)
+    for b in range(batch):
+      f = noff + (0 if shared else b)
+      if f >= n_feature:
+        continue
+      f0 = int(feature_offset[f])
+      f1 = int(feature_offset[f + 1]) if f < n_feature - 1 else n_fid
+      if f1 <= f0:
+        continue
+      rows = [(int(fid_offset[q]) >> 32, int(fid_offset[q]) & 0xffffffff) for q in range(f0, f1)]
+      valid = [(i1, i2) for (i1, i2) in rows if i1 < len(embs)]
+      at = b * stride + int(sc.out_offset)
+      if sc.pooling == FIRSTN:
+        for s_, (i1, i2) in enumerate(valid[:int(sc.max_sequence_length)]):
+          outs[sc.out_index][at + s_ * dim:at + (s_ + 1) * dim] = embs[i1][i2, start:start + dim]
+        continue
+      acc = np.zeros(dim, np.float32) if not valid else None
+      for (i1, i2) in valid:
+        x = embs[i1][i2, start:start + dim]
+        if sc.pooling == MEAN:
+          x = x / np.float32(len(rows))
+        acc = x.copy() if acc is None else acc + x
+      if sc.out_type == ADDN:
+        outs[sc.out_index][at:at + dim] += acc
+      else:
+        outs[sc.out_index][at:at + dim] = acc
   return outs
 
 

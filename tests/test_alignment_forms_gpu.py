@@ -17,6 +17,9 @@ misaligned one ``lookup_kernel``; five 1024-position dedup workgroups), ids Zipf
 third one the same id (one list of ~1367 occurrences: heavy, six 256-entry chunks), three steps.
 Dims of float4-capable tables 4 (G 8), 64 (G 16), 68 / 128 (G 32), 132 / 256 (G 64), and one table
 that can never be float4: bias FTRL(1) + Adagrad(16), dim 17.
+
+The layout op (section g) has no table: six one-fid slices of widths 4 .. 260 at batch 33, the shapes and the
+raw caller of tests/test_layout_forms_gpu.py.
 """
 import numpy as np
 import pytest
@@ -612,3 +615,54 @@ def test_fused_apply_gradient_with_misaligned_id_grads(unique):
       np.testing.assert_array_equal(r.cpu().numpy()[a], o_rows[b], err_msg="%s mis %s" % (n, mis))
   for a, b in zip(rows[True], rows[False]):
     np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+# ===================================================================== g. fused_embedding_to_layout
+from oracle import layout as OL  # noqa: E402
+from test_layout_forms_gpu import (CYCLE, FLAG, dev_inputs, one_fid_case, output_grads, planned,  # noqa: E402
+                                   raw_forward, raw_grad, same_bits)
+
+
+def _layout_case(with_bias):
+  """Six one-fid features, slice widths 4, 12, 260, 16, 64, 4 from columns 0, 4, 8 of rows 4 floats wider,
+  one CONCAT layout; ``with_bias``: an ADDN layout of every row's last float too — an output of ``batch`` =
+  33 floats, so the zero fill has a tail behind its float4s when the buffer is aligned and takes its scalar
+  branch when it is not (a one-wide slice also sends the whole launch to the general kernels)."""
+  widths = CYCLE + [4]
+  starts = [4 * (i % 3) for i in range(6)]
+  strides = [s + w + 4 for s, w in zip(starts, widths)]
+  layouts = {"vec": (OL.CONCAT, [(i, s, s + w) for i, (s, w) in enumerate(zip(starts, widths))], None)}
+  if with_bias:
+    layouts["bias"] = (OL.ADDN, [(i, strides[i] - 1, strides[i]) for i in range(6)], None)
+  return one_fid_case(31, 33, strides, layouts)
+
+
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("which", ["emb", "out", "tensors_grad", "grad_out", "all"])
+def test_layout_entry_points_with_misaligned_buffers(which, with_bias):
+  """``mhte_embedding_to_layout`` / ``_grad`` with one embedding matrix, one output, the output gradients, the
+  gradient buffers or all of them one float off alignment, with MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS (the
+  float4 forms must give way to ``layout_kernel``) and without: the bits of the all-aligned run and of
+  the oracle; outputs and gradient buffers hold NaN before the call."""
+  c = _layout_case(with_bias)
+  slices, shapes, lens = planned(c)
+  every = which == "all"
+  embs = [_buf(e, every or (which == "emb" and i == 2)) for i, e in enumerate(c["embs"])]
+  d, d_al = dev_inputs(c, embs), dev_inputs(c)
+  assert all(e.data_ptr() % 16 == 0 for e in d_al["embs"])
+  tg = output_grads(shapes, 4)
+  want = OL.layout_model(c["embs"], c["fid_offset"], c["feature_offset"], c["nfl_offset"], c["batch"], c["cfgs"])
+  gwant = OL.layout_grad_model(c["embs"], c["fid_offset"], c["feature_offset"], c["nfl_offset"], c["batch"], c["cfgs"],
+                               tg, acc_dtype=np.float32)
+  for flag in (FLAG, 0):
+    outs = [_mis_empty(n) if (every or (which == "out" and k == 0)) else torch.empty(n, device="cuda")
+            for k, n in enumerate(lens)]
+    got = raw_forward(d, slices, lens, flag, outs=outs)
+    same_bits(got, want, "forward flag %d" % flag)
+    same_bits(got, raw_forward(d_al, slices, lens, flag), "forward flag %d against the aligned run" % flag)
+    dtg = [_buf(t, every or which == "tensors_grad") for t in tg]
+    grads = [_mis_empty(*e.shape) if (every or which == "grad_out") else torch.empty(e.shape, device="cuda")
+             for e in c["embs"]]
+    gg = raw_grad(d, slices, dtg, flag, grads=grads)
+    same_bits(gg, gwant, "gradient flag %d" % flag)
+    same_bits(gg, raw_grad(d_al, slices, [_al(t) for t in tg], flag), "gradient flag %d against the aligned run" % flag)

@@ -875,7 +875,10 @@ def test_fused_embedding_to_layout_grad_heavy_rows():
 
 def test_fused_embedding_to_layout_copy_form():
   """MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS: one fid per feature instance, unique rows, float4-aligned
-  slices — the vector copy form (plain stores in the gradient) equals the general form."""
+  slices — the vector copy form (plain stores in the gradient) equals the general form.  With 28 float4
+  columns per batch row this runs ``layout_rows_kernel`` (forward: whole rows, no fill in front), not
+  ``layout_copy_kernel``, which takes launches of more than 2048 columns: tests/test_layout_forms_gpu.py
+  cases (b) and (g)."""
   from monolith_amd import distribution_ops as D
   rng = np.random.default_rng(4)
   B, dims = 257, [16, 32, 64]
