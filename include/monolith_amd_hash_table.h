@@ -272,6 +272,17 @@ mhte_status mhte_table_contains(mhte_multi_table* t, int32_t table, const int64_
  * table's own fuzzy max of all update_times seen (tf_bridge.cc:262-263). */
 mhte_status mhte_table_evict(mhte_multi_table* t, int32_t table, int64_t max_update_time,
                              void* stream);
+/* Compaction: eviction empties bucket slots but the rows of the evicted ids stay allocated.  This moves
+ * the rows of the live entries into the lowest row handles and releases the row slabs above them; keys,
+ * bucket positions, timestamps, dump order and every row's bits are unchanged.  Safe between any two
+ * calls: whatever was resolved ahead against the table (a step's hints, rows reserved for the next
+ * batch) is resolved again.  FAILED_PRECONDITION on a capturing stream.
+ * out[0] = row handles in use before, [1] = after (= live keys, + 1 when the reserved key is stored),
+ * [2] = rows moved, [3] = bytes of row slabs released.  Synchronises the stream. */
+mhte_status mhte_table_compact(mhte_multi_table* t, int32_t table, int64_t out[4], void* stream);
+/* min_free_fraction in (0, 1]: after every eviction scan of this table (cadence or explicit) compact
+ * when (handles in use - live) / handles in use >= it.  0 (default): never. */
+mhte_status mhte_table_set_auto_compact(mhte_multi_table* t, int32_t table, double min_free_fraction);
 /* Table geometry: hashpower, rows allocated, lookup hits since last call. Synchronises. */
 typedef struct {
   int64_t size;

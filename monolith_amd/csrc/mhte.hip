@@ -44,6 +44,7 @@
 #include "mhte_step_kernels.h"
 #include "mhte_mstep_kernels.h"
 #include "mhte_shard_kernels.h"
+#include "mhte_compact_kernels.h"
 #include "mhte_gemm_kernels.h"
 
 namespace mhte {
@@ -1532,6 +1533,149 @@ struct Table {
     evict_kernel<<<dim3(uint32_t(std::min<uint64_t>(need, 2048))), 256, 0, st>>>(
         view, max_ts < 0 ? max_update_ts : max_ts, ttl);
     HIP_OK(hipGetLastError());
+    // opt-in (mhte_table_set_auto_compact): the scan may have freed enough rows to be worth a compaction.
+    // Unset — the default — the scan stays what it was: one launch, no host wait.
+    if (auto_compact > 0.0) {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return;
+      sync_counters(st);
+      const uint64_t in_use = h_ctr->alloc & 0xffffffffull;
+      const uint64_t live = uint64_t(live_keys()) + (h_ctr->special_state == 1 ? 1 : 0);
+      if (in_use > live && double(in_use - live) >= auto_compact * double(in_use)) {
+        int64_t res[4];
+        compact(res, st);
+      }
+    }
+  }
+
+  // Compaction: the rows of the live entries move into the lowest row handles (mhte_compact_kernels.h)
+  // and the slabs above them are released.  Keys, bucket positions, timestamps, dump order and every
+  // row's bits stay; only row handles change.  Everything that holds a handle from before is made void:
+  // the epoch moves (the multi-table and the id-sharded step hand their hints over only while it stands
+  // still) and the counters are registered anew, as in clear() — to a workspace that was numbered and
+  // probed before, the table is another one: it probes again, and the rows it had reserved (handles in
+  // no bucket, now possibly given to a survivor) are dropped with their keys taken off the live count.
+  // out: handles in use before, after, rows moved, bytes of slabs released.
+  double auto_compact = 0.0;   // mhte_table_set_auto_compact: free fraction at which evict() compacts (0: never)
+  void compact(int64_t out[4], hipStream_t st) {
+    {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        throw Error(MHTE_FAILED_PRECONDITION,
+                    "table " + name + ": a compaction moves rows and releases slabs, which cannot be "
+                    "captured into a hipGraph");
+    }
+    finish_pending(st);
+    sync_counters(st);
+    ++mut_epoch;
+    const uint64_t in_use = h_ctr->alloc & 0xffffffffull;
+    const bool spec = h_ctr->special_state == 1;
+    const uint64_t live = uint64_t(live_keys()) + (spec ? 1 : 0);
+    out[0] = out[1] = int64_t(in_use);
+    out[2] = out[3] = 0;
+    if (in_use == live) return;
+    const uint64_t row_cap = uint64_t(chunks.size()) << chunk_shift;
+    if (live > in_use || in_use > row_cap)
+      throw Error(MHTE_INTERNAL, "table " + name + ": compact: " + std::to_string(live) + " live entries, " +
+                                     std::to_string(in_use) + " row handles in use, room for " +
+                                     std::to_string(row_cap));
+    const uint32_t L = uint32_t(live);
+    uint32_t n_slot_movers = 0, special_src = kNoRow;
+    DevBuf<uint32_t> bitmap, tile_movers, tile_holes, holes, mv_src;
+    DevBuf<uint64_t> mv_slot;
+    if (L > 0) {
+      const uint64_t nslots = (uint64_t(1) << hp) * kSlots;
+      const uint64_t ntiles = (nslots + kCompactTileSlots - 1) / kCompactTileSlots;
+      const uint32_t nwords = (L + 31u) / 32u;
+      const uint32_t nhtiles = (nwords + kCompactTileWords - 1) / kCompactTileWords;
+      const uint32_t grid_s = uint32_t(std::min<uint64_t>(ntiles, 2048));
+      const uint32_t grid_h = std::min<uint32_t>(nhtiles, 2048);
+      bitmap.reserve(nwords);
+      tile_movers.reserve(ntiles);
+      tile_holes.reserve(nhtiles);
+      HIP_OK(hipMemsetAsync(bitmap.p, 0, sizeof(uint32_t) * nwords, st));
+      compact_mark_kernel<<<grid_s, 256, 0, st>>>(view, L, ntiles, bitmap.p, tile_movers.p);
+      HIP_OK(hipGetLastError());
+      compact_hole_count_kernel<<<grid_h, 256, 0, st>>>(bitmap.p, nwords, L, nhtiles, tile_holes.p);
+      HIP_OK(hipGetLastError());
+      std::vector<uint32_t> hm(ntiles), hh(nhtiles);
+      HIP_OK(hipMemcpyAsync(hm.data(), tile_movers.p, sizeof(uint32_t) * ntiles, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(hh.data(), tile_holes.p, sizeof(uint32_t) * nhtiles, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      // exclusive scans, in place (a cold path, as in dump)
+      uint64_t n_m = 0, n_h = 0;
+      for (uint32_t& c : hm) {
+        const uint32_t v = c;
+        c = uint32_t(n_m);
+        n_m += v;
+      }
+      for (uint32_t& c : hh) {
+        const uint32_t v = c;
+        c = uint32_t(n_h);
+        n_h += v;
+      }
+      if (spec && h_ctr->special_row >= L) special_src = h_ctr->special_row;
+      const uint64_t n_movers = n_m + (special_src != kNoRow ? 1 : 0);
+      // one hole per mover: holds when the handles in the buckets are distinct and the counters true
+      if (n_movers != n_h)
+        throw Error(MHTE_INTERNAL, "table " + name + ": compact: " + std::to_string(n_movers) + " rows above handle " +
+                                       std::to_string(L) + " but " + std::to_string(n_h) + " free handles below it");
+      n_slot_movers = uint32_t(n_m);
+      if (n_movers) {
+        holes.reserve(n_movers);
+        mv_slot.reserve(n_m + 1);
+        mv_src.reserve(n_m + 1);
+        HIP_OK(hipMemcpyAsync(tile_holes.p, hh.data(), sizeof(uint32_t) * nhtiles, hipMemcpyHostToDevice, st));
+        compact_hole_emit_kernel<<<grid_h, 256, 0, st>>>(bitmap.p, nwords, L, nhtiles, tile_holes.p, holes.p,
+                                                         uint32_t(n_movers));
+        HIP_OK(hipGetLastError());
+        if (n_m) {
+          HIP_OK(hipMemcpyAsync(tile_movers.p, hm.data(), sizeof(uint32_t) * ntiles, hipMemcpyHostToDevice, st));
+          compact_mover_emit_kernel<<<grid_s, 256, 0, st>>>(view, L, ntiles, tile_movers.p, mv_slot.p, mv_src.p,
+                                                            n_slot_movers);
+          HIP_OK(hipGetLastError());
+        }
+        // a group of G lanes per row, one copy unit (float4, or a float) per lane and trip
+        const bool vec = row_floats % 4 == 0;
+        const uint32_t units = vec ? row_floats / 4 : row_floats;
+        const uint32_t G = std::min<uint32_t>(64, 1u << ceil_log2(units));
+        const uint64_t wgs = (n_movers * G + 255) / 256;
+        const uint32_t grid_m = uint32_t(std::min<uint64_t>(wgs, uint64_t(8) * num_cus));
+        if (vec)
+          compact_move_kernel<4><<<grid_m, 256, 0, st>>>(view, mv_slot.p, mv_src.p, holes.p, n_slot_movers,
+                                                         special_src, L, row_cap, G);
+        else
+          compact_move_kernel<1><<<grid_m, 256, 0, st>>>(view, mv_slot.p, mv_src.p, holes.p, n_slot_movers,
+                                                         special_src, L, row_cap, G);
+        HIP_OK(hipGetLastError());
+      }
+    }
+    compact_counters_kernel<<<1, 64, 0, st>>>(ctr, L);
+    HIP_OK(hipGetLastError());
+    // (the stream, then — inside hipFree — the device: a step's side stream has nothing of this table's
+    // in flight that outlives that, which is what double_table relies on for the old bucket array)
+    HIP_OK(hipStreamSynchronize(st));
+    const size_t keep =
+        std::max<size_t>(1, size_t((uint64_t(L) + kSpecSlackRows + (uint64_t(1) << chunk_shift) - 1) >> chunk_shift));
+    const size_t slab_bytes = (size_t(1) << chunk_shift) * row_floats * sizeof(float);
+    size_t released = 0;
+    if (chunks.size() > keep) {
+      HIP_OK(hipMemset(d_chunks + keep, 0, sizeof(float*) * (chunks.size() - keep)));
+      while (chunks.size() > keep) {
+        HIP_OK(hipFree(chunks.back()));
+        chunks.pop_back();
+        released += slab_bytes;
+      }
+    }
+    unregister_counters(ctr, ctr_serial);
+    ctr_serial = register_counters(ctr);
+    sync_counters(st);
+    keys_upper = uint64_t(live_keys());
+    rows_upper = h_ctr->alloc & 0xffffffffull;
+    refresh_view();
+    out[1] = int64_t(L);
+    out[2] = int64_t(n_slot_movers) + (special_src != kNoRow ? 1 : 0);
+    out[3] = int64_t(released);
   }
 };
 
@@ -2091,6 +2235,26 @@ mhte_status mhte_table_evict(mhte_multi_table* t, int32_t table, int64_t max_upd
     HIP_OK(hipSetDevice(t->device));
     std::lock_guard<std::mutex> g(tb.mu);
     tb.evict(max_update_time, S(stream));
+  });
+}
+
+mhte_status mhte_table_compact(mhte_multi_table* t, int32_t table, int64_t out[4], void* stream) {
+  return guard([&] {
+    Table& tb = table_at(t, table);
+    if (!out) throw Error(MHTE_INVALID_ARGUMENT, "compact: null argument");
+    HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> g(tb.mu);
+    tb.compact(out, S(stream));
+  });
+}
+
+mhte_status mhte_table_set_auto_compact(mhte_multi_table* t, int32_t table, double min_free_fraction) {
+  return guard([&] {
+    Table& tb = table_at(t, table);
+    if (!(min_free_fraction >= 0.0 && min_free_fraction <= 1.0))
+      throw Error(MHTE_INVALID_ARGUMENT, "set_auto_compact: min_free_fraction must be 0 (never) or in (0, 1]");
+    std::lock_guard<std::mutex> g(tb.mu);
+    tb.auto_compact = min_free_fraction;
   });
 }
 

@@ -621,6 +621,20 @@ class MultiHashTable:
     check(self._lib.mhte_table_evict(self._h, self._index(name), int(max_update_time), _stream()))
     return self
 
+  def compact(self, name: str) -> dict:
+    """Reclaims the rows of evicted ids (mhte_table_compact): the live rows move into the lowest row
+    handles and the slabs above them are released.  Lookups, dumps and checkpoints are unchanged."""
+    out = (C.c_int64 * 4)()
+    check(self._lib.mhte_table_compact(self._h, self._index(name), out, _stream()))
+    return dict(rows_before=int(out[0]), rows_after=int(out[1]), rows_moved=int(out[2]),
+                bytes_released=int(out[3]))
+
+  def set_auto_compact(self, name: str, min_free_fraction: float) -> "MultiHashTable":
+    """Compact after an eviction scan that leaves at least this fraction of the row handles in use
+    without an entry (mhte_table_set_auto_compact); 0, the default: never."""
+    check(self._lib.mhte_table_set_auto_compact(self._h, self._index(name), float(min_free_fraction)))
+    return self
+
   def dump(self, name: str, with_rows: bool = True):
     """(ids, positions=bucket*4+slot, ts, rows[n, dim+state]) in bucket-major order."""
     i = self._index(name)
