@@ -312,13 +312,22 @@ int32_t mhte_table_row_floats(const mhte_multi_table* t, int32_t i);
 /* ---- the step right after the exchange: gather per merged slot, its gradient, ragged reductions --
  * MonolithFusedGatherEmbeddingsByInput (+Gradient) (RT/ops/map_id_to_embedding.cu.cc:31-118,
  * NT/distribution_ops.py:671-686): outputs[i][j, :] = fused_embeddings[offsets[i][j] + 0 .. dims[i]);
- * gradient: fused_grad (zero-filled, fused_len floats) += grads[i][j, :] * scale at the same offsets
- * (float atomics, as the reference's GpuAtomicAdd).  offsets / outputs / grads: HOST arrays of
- * n_inputs device pointers; n, dims: host arrays.
+ * gradient: fused_grad (zero-filled here, fused_len floats) += grads[i][j, :] * scale at the same
+ * offsets.  No float atomics: the rows that share a destination are grouped and added in row order
+ * (rows numbered input after input; acc = 0, acc = acc + g * scale, the product rounded first), each
+ * row with its own dims[i] columns, then fused_grad += acc.  Inputs are taken in chunks of 32, added
+ * chunk after chunk.  Precondition: two rows either share an offset or their ranges
+ * [offset, offset + dim) are disjoint, and every range lies inside fused_len.
+ * MHTE_POOL_ATOMICS=1 (read once per process) selects the atomic forms of the gradient and of the
+ * unsorted reduction instead: the reference's GpuAtomicAdd, arrival order.
+ * offsets / outputs / grads: HOST arrays of n_inputs device pointers; n, dims: host arrays.
  * MonolithReduceSum / ReduceMean / ReduceSquareNorm (RT/ops/reduce_op.cc:29-125,
  * NT/embedding_combiners.py:41-102): out[b, :] over the rows i with indices[i] == b; mode 0 sum,
- * 1 mean, 2 sqrt of the sum of squares.  indices_sorted != 0 (the layout sparse/ragged inputs
- * have): sequential in-order accumulation, bit-identical to the reference; otherwise atomics. */
+ * 1 mean (an empty output is NaN), 2 sqrt of the sum of squares.  Both default forms add the rows of
+ * an output in index order, bit-identical to the reference's sequential loop: indices_sorted != 0
+ * (the layout sparse/ragged inputs have) finds each output's segment by binary search, otherwise the
+ * rows are grouped by a stable sort first.  Both ignore an index outside [0, batch); the atomic form
+ * uses the index as an address unchecked, as the reference does. */
 mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
                                                   const int32_t* const* offsets, const int64_t* n,
                                                   const int32_t* dims, float* const* outputs,

@@ -26,9 +26,13 @@ struct GatherInputs {
 
 // MonolithFusedGatherEmbeddingsByInput: outputs[i][j, :] = fused[offsets[i][j] + 0 .. dim_i)
 // (map_id_to_embedding.cu.cc:31-72).  One thread per element would re-read the offset dim times;
-// here a lane group takes one row.  GATHER = false: the gradient,
-// fused_grad[offsets[i][j] + k] += grads[i][j, k] * scale (:74-118) — float atomics, like the
-// reference's GpuAtomicAdd (rows that share an offset are added in arrival order).
+// here a lane group takes one row.  GATHER = false: the gradient in its float-atomic form,
+// fused_grad[offsets[i][j] + k] += grads[i][j, k] * scale (:74-118) with atomicAdd, like the
+// reference's GpuAtomicAdd (rows that share an offset are added in arrival order).  It runs only
+// under MHTE_POOL_ATOMICS=1; the default gradient is the pair of list kernels below: the rows that
+// share a destination are grouped and added in row order, inputs taken in chunks of
+// kMaxGatherInputs, chunk after chunk.  Precondition of the list kernels: two rows either share
+// an offset or their ranges [offset, offset + dim) are disjoint (a key is as wide as its widest row).
 // A row whose offset and dim are multiples of 4 floats moves as float4s (in.aligned: the host
 // found every base pointer 16-byte aligned); any other row takes the scalar loop.
 // MonolithHashTableLookupGradient (RT/ops/hash_table_lookup_op.cc:110-147): out_ids[i] = id_values[i],
@@ -339,7 +343,15 @@ __global__ __launch_bounds__(256) void gather_grad_lists_vec_kernel(float* __res
   for (int t = 0; t < K; ++t) {
     if (fast[t] || s0[t] >= s1[t]) continue;
     const int64_t o = off[t];
-    const int d0 = dim[t];
+    int d0 = dim[t];
+    if (s1[t] - s0[t] > 1u) {
+      // several addends, perhaps of inputs of different widths: the key is as wide as its widest addend (the
+      // reference adds every element of every row, map_id_to_embedding.cu.cc:105-117).  The lanes of the
+      // group share the scan of the list; a single addend never comes here with more than its own dim.
+      for (uint32_t q = s0[t] + 1u + uint32_t(j); q < s1[t]; q += G) d0 = max(d0, s_dim[input_of(seg_pos[q])]);
+#pragma unroll
+      for (int x = G / 2; x >= 1; x >>= 1) d0 = max(d0, __shfl_xor(d0, x, G));
+    }
     if (o & 3) {   // a destination that is not 16-byte aligned: one float per lane
       for (int k = j; k < d0; k += G) {
         float acc = 0.f;
@@ -409,6 +421,16 @@ __global__ __launch_bounds__(256) void gather_grad_lists_kernel(float* __restric
     int i = 0;
     while (in.start[i + 1] <= r) ++i;
     dim = in.dim[i];
+  }
+  if (s1 - s0 > 1u) {   // the key is as wide as its widest addend; the lanes of the group share the scan
+    for (uint32_t q = s0 + 1u + uint32_t(j); q < s1; q += G) {
+      const int64_t r = seg_pos[q];
+      int i = 0;
+      while (in.start[i + 1] <= r) ++i;
+      dim = max(dim, in.dim[i]);
+    }
+#pragma unroll
+    for (int x = G / 2; x >= 1; x >>= 1) dim = max(dim, __shfl_xor(dim, x, G));
   }
   for (int k = j; k < dim; k += G) {
     float acc = 0.f;

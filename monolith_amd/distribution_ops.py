@@ -273,7 +273,11 @@ def fused_gather_embeddings_by_input(fused_embeddings: torch.Tensor,
 def fused_gather_embeddings_by_input_gradient(fused_embeddings_size: int, grads: List[torch.Tensor],
                                               embedding_offsets: List[torch.Tensor],
                                               embedding_dims: List[int], scale=1.0):
-  """reference :678-686: the flat gradient of the fused buffer (float atomics, like the reference).
+  """reference :678-686: the flat gradient of the fused buffer.  No float atomics: rows that share an
+  offset are grouped and added in row order (rows numbered input after input, ``acc = acc + g * scale``
+  from 0, each row with its own dim columns), inputs taken in chunks of 32, added chunk after chunk.
+  Two rows must either share an offset or cover disjoint ranges.  ``MHTE_POOL_ATOMICS=1`` selects the
+  reference's atomic form (arrival order).
   ``scale``: a Python float, or a 0-d float32 device tensor (``clip_ops.global_norm_and_scale``) that is
   read on the device — nothing comes back to the host and a captured graph replays with its current value."""
   dev = grads[0].device
