@@ -142,7 +142,9 @@ void mhte_multi_table_destroy(mhte_multi_table* t);
  * is the filter_handle input; its occurrence thresholds (mhte_hash_filter_create_from_proto) become
  * the tables'.  reserve_rows / max_load_factor: the MI355X extensions of mhte_table_config, applied to
  * every table (0: defaults).  learning_rates_out (optional, host float[cap]) receives the configs' own
- * per-segment learning rates in table order (the ops take the live values as an input). */
+ * per-segment learning rates in table order (the ops take the live values as an input).
+ * Segment.comp_config picks each segment's training retriever as the reference does
+ * (RT/hash_table/entry_accessor.cc:283-302; mhte_table_set_retriever below). */
 mhte_status mhte_multi_table_create_from_proto(const void* config, int64_t config_len,
                                                mhte_hash_filter* filter, uint64_t reserve_rows,
                                                float max_load_factor, int32_t device,
@@ -922,6 +924,51 @@ mhte_status mhte_shard_group_backward(mhte_shard_step** steps, int32_t n, const 
  * the step kernels' FULL instantiations).  0, and 2 for the unpipelined mhte_table_sum_optimize_n:
  * segment sum + optimize, which needs the ordered mhte_unique. */
 int32_t mhte_table_fused_backward_ok(const mhte_multi_table* t, int32_t i);
+
+/* ---- Quantization-aware training: the segment retrievers of a TRAINING table ------------------
+ * The reference's EntryAccessor reads a row through a retriever (Retrieve in the lookup,
+ * RT/hash_table/entry_accessor.cc:169-171; Backward in front of the optimizer, :187-195) that it picks
+ * per segment from the segment's comp_config (:283-302; retrievers combine per segment,
+ * CombineRetrievers): fixed_r8 ("qat8 in Bytedance PS", compressor/float_compressor.proto:29-33) ->
+ * the fake-quant retriever, one_bit -> the HashNet retriever, fp32 / fp16 / none -> the raw one (the
+ * compressor itself matters for SERVING entries only, which stay refused).  Rows stay fp32 in HBM.
+ *   MHTE_RETRIEVER_FAKE_QUANT_R8  params {r}.  Lookups return FakeQuantizer(r).Quantize(w)
+ *       (compressor/fake_quantizer.h:26-70): step = r / 128; NaN -> 0; w +- step / 2 by sign; the
+ *       correctly rounded fp32 quotient by step truncated THROUGH AN INTEGER (-0.0 and small negatives
+ *       give +0.0), clamped to [-128, 127], times step.  Backward is a no-op
+ *       (retriever/fake_quant_retriever.cc:38-39).  A quotient outside int range, or +-inf, is undefined
+ *       behaviour in the reference; here it saturates by sign (+127 * step, -128 * step).
+ *   MHTE_RETRIEVER_HASH_NET       params {step_size, init_scale, max_scale, amplitude}
+ *       (compressor/hash_net_quantizer.h:33-70).  Lookups return amplitude * tanhf(scale * w).  An
+ *       Optimize first runs Backward per element on every gradient it hands to the optimizer (each
+ *       occurrence's, or the sum's under MHTE_SUM_DUPLICATES / mhte_table_sum_optimize_n): where
+ *       global_step % step_size == 0, scale = min(init_scale * powf(1 + 0.005 * global_step, 0.5),
+ *       max_scale); then g *= amplitude * scale * (1 - tanhf(scale * w)^2), w the stored weight at that
+ *       moment (a new id's: the initializer's value, RT/hash_table/cuckoo_embedding_hash_table.cc:346-353;
+ *       a sequential duplicate's: the weight the previous occurrence left).  `scale` is state of the
+ *       (table, segment): it starts at init_scale, lookups read the live value, it moves only in a
+ *       call in which an id reaches the optimizer (not with n = 0, not when the admission filter drops
+ *       every id), and it is not part of a checkpoint.  step_size <= 0 (a division by zero in the
+ *       reference) and a GROUP_ADAGRAD segment: MHTE_INVALID_ARGUMENT.
+ * Not replicated: the reference scales the CALLER's gradient tensor in place through a const_cast
+ * (entry_accessor.cc:190-192); here the caller's buffer is not written.
+ * Save / LookupEntry / dump read the stored weights (GetNum, entry_accessor.cc:225-232); Assign,
+ * AssignAdd and Reinitialize write them raw.
+ * A table with a non-raw retriever does not satisfy mhte_table_fused_backward_ok;
+ * mhte_table_step_forward / _backward, mhte_multi_step_create and mhte_shard_step_create(_ipc) refuse
+ * it by name (their kernels read rows raw), and the setter refuses a MultiHashTable that already has a
+ * multi-table or id-sharded step (MHTE_FAILED_PRECONDITION).
+ * mhte_table_set_retriever runs under the table's lock, behind the table's enqueued work, and has
+ * taken effect when it returns; it (re)sets the segment's scale to init_scale.
+ * mhte_table_get_retriever: the type and up to `cap` of its parameters.
+ * mhte_table_hash_net_scale: the live scale of a HashNet segment into host memory; synchronises. */
+enum { MHTE_RETRIEVER_RAW = 0, MHTE_RETRIEVER_FAKE_QUANT_R8 = 1, MHTE_RETRIEVER_HASH_NET = 2 };
+mhte_status mhte_table_set_retriever(mhte_multi_table* t, int32_t table, int32_t segment, int32_t type,
+                                     const float* params, int32_t n_params);
+mhte_status mhte_table_get_retriever(mhte_multi_table* t, int32_t table, int32_t segment, int32_t* type,
+                                     float* params, int32_t cap);
+mhte_status mhte_table_hash_net_scale(mhte_multi_table* t, int32_t table, int32_t segment, float* host_out,
+                                      void* stream);
 
 /* MonolithUniqueKeyWithValueAndOffset (RT/ops/unique_mapping_ops.cc:51-155), one table at a time:
  * value_offset[q] = value_base + position*dim for the occurrence lists, value_offset_split[u] =

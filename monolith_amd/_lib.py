@@ -34,6 +34,7 @@ OPT_SGD, OPT_ADAGRAD, OPT_FTRL = 0, 1, 2
 OPT_MOMENTUM, OPT_ADADELTA, OPT_RMSPROP, OPT_RMSPROPV2, OPT_ADAM, OPT_AMSGRAD = 3, 4, 5, 6, 7, 8
 OPT_MOVING_AVERAGE, OPT_BATCH_SOFTMAX, OPT_GROUP_ADAGRAD = 9, 10, 11
 OPT_FLAG_STOCHASTIC_ROUNDING_FP16 = 0x100   # OR-ed into opt_type
+MHTE_RETRIEVER_RAW, MHTE_RETRIEVER_FAKE_QUANT_R8, MHTE_RETRIEVER_HASH_NET = 0, 1, 2
 INIT_ZEROS, INIT_ONES, INIT_CONSTANT, INIT_RANDOM_UNIFORM = 0, 1, 2, 3
 
 

@@ -753,7 +753,102 @@ struct Table {
   DevBuf<int64_t> d_occ_slots;
   DevBuf<int32_t> d_occ_thr;
   bool has_group_opt = false;       // a segment uses GroupAdaGrad (picks the kernel instantiation)
-  uint32_t* flt_slots = nullptr;    // owned by the mhte_hash_filter attached to the MultiHashTable
+  // Segment retrievers (quantization-aware training, mhte_qat_kernels.h; mhte_table_set_retriever).
+  // params: fake quant {r}; hash net {step_size, init_scale, max_scale, amplitude}.
+  struct Retriever {
+    int32_t type = kRetRaw;
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+  };
+  std::vector<Retriever> retrievers;   // one per segment
+  bool has_retriever = false;          // a segment's retriever is not the raw one
+  bool has_hash_net = false;           // ... is HashNet: the update kernels run its Backward
+  float* d_scale = nullptr;            // [kMaxSegments] live HashNet scales (allocated with the first HashNet segment)
+  static const char* retriever_name(int32_t type) {
+    return type == kRetFakeQuant ? "fake_quant_r8" : (type == kRetHashNet ? "hash_net" : "raw");
+  }
+  // the fused step kernels and the step objects read rows raw: a table with a retriever is refused there, by name
+  void refuse_retriever(const std::string& what) const {
+    for (uint32_t k = 0; k < uint32_t(retrievers.size()); ++k)
+      if (retrievers[k].type != kRetRaw)
+        throw Error(MHTE_INVALID_ARGUMENT,
+                    what + ": table " + name + " has a " + retriever_name(retrievers[k].type) + " retriever on segment " +
+                        std::to_string(k) + "; the fused step kernels read rows raw — such a table takes the op-level "
+                        "lookup and update (mhte_lookup / mhte_table_lookup_n, mhte_optimize / mhte_table_optimize_n / "
+                        "mhte_table_sum_optimize_n)");
+  }
+  void set_retriever(int32_t k, int32_t type, const float* params, int32_t n_params) {
+    if (k < 0 || k >= int32_t(nseg))
+      throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: table " + name + " has no segment " + std::to_string(k));
+    Retriever r;
+    r.type = type;
+    if (type == kRetFakeQuant) {
+      if (!params || n_params != 1)
+        throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: fake_quant_r8 takes 1 parameter {r}");
+      if (!(params[0] > 0.f) || std::isinf(params[0]))
+        throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: fake_quant_r8 needs a finite r > 0");
+      r.p[0] = params[0];
+    } else if (type == kRetHashNet) {
+      if (!params || n_params != 4)
+        throw Error(MHTE_INVALID_ARGUMENT,
+                    "set_retriever: hash_net takes 4 parameters {step_size, init_scale, max_scale, amplitude}");
+      // (global_step % step_size: the reference divides by zero, hash_net_quantizer.h:47)
+      if (!(params[0] >= 1.f)) throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: hash_net needs step_size > 0");
+      // (it travels as a float: whole numbers up to 2^24 are exact, anything else would be another schedule)
+      if (params[0] > 16777216.f || params[0] != floorf(params[0]))
+        throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: hash_net step_size must be a whole number <= 2^24");
+      if (view.seg[k].opt == kOptGroupAdagrad)
+        throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: hash_net on a group_adagrad segment is not implemented "
+                                           "(the whole-segment update has no per-element Backward)");
+      for (int i = 0; i < 4; ++i) r.p[i] = params[i];
+    } else if (type != kRetRaw) {
+      throw Error(MHTE_INVALID_ARGUMENT, "set_retriever: unknown retriever type " + std::to_string(type));
+    }
+    finish_pending(nullptr);
+    if (type == kRetHashNet && !d_scale) {
+      HIP_OK(hipMalloc(&d_scale, sizeof(float) * kMaxSegments));
+      HIP_OK(hipMemset(d_scale, 0, sizeof(float) * kMaxSegments));
+    }
+    // (the setter has no stream: the device is drained first, so the change is behind all enqueued work of
+    // every stream, non-blocking ones included, and in place at return)
+    HIP_OK(hipDeviceSynchronize());
+    if (type == kRetHashNet) HIP_OK(hipMemcpy(d_scale + k, &r.p[1], sizeof(float), hipMemcpyHostToDevice));
+    retrievers[k] = r;
+    has_retriever = has_hash_net = false;
+    for (const Retriever& x : retrievers) {
+      has_retriever = has_retriever || x.type != kRetRaw;
+      has_hash_net = has_hash_net || x.type == kRetHashNet;
+    }
+  }
+  // The descriptors of a launch.  global_step (updates): the candidate scale of every HashNet segment whose
+  // step_size divides it (HashNetQuantizer::Backward, hash_net_quantizer.h:47-50: powf, then the cap).
+  RetrieverArgs retriever_args(bool update, int64_t global_step) const {
+    RetrieverArgs ra{};
+    ra.nseg = nseg;
+    ra.scale = d_scale;
+    for (uint32_t k = 0; k < nseg; ++k) {
+      const Retriever& r = retrievers[k];
+      ra.type[k] = r.type;
+      ra.w_off[k] = uint32_t(view.seg[k].w_off);
+      if (r.type == kRetFakeQuant) {   // FakeQuantizer's constructor, fake_quantizer.h:28-29
+        ra.p0[k] = r.p[0] / 128;
+        ra.p1[k] = ra.p0[k] / 2;
+      } else if (r.type == kRetHashNet) {
+        ra.p0[k] = r.p[3];
+        if (update && global_step % int64_t(r.p[0]) == 0) {
+          ra.cand[k] = std::min(r.p[1] * powf(1.f + 0.005f * static_cast<float>(global_step), 0.5f), r.p[2]);
+          ra.update |= 1u << k;
+        }
+      }
+    }
+    return ra;
+  }
+  // the kernel instance the table's retrievers select: lookups, and (hash net only) updates
+  int retriever_instance(bool update) const {
+    if (update ? !has_hash_net : !has_retriever) return kRtRaw;
+    if (nseg == 1) return retrievers[0].type == kRetFakeQuant ? kRtFakeQuant : kRtHashNet;
+    return kRtMixed;
+  }
+  uint32_t* flt_slots = nullptr;   // owned by the mhte_hash_filter attached to the MultiHashTable
   uint64_t flt_total = 0;
   uint32_t* flt_state = nullptr;
   uint32_t flt_nsplit = 0, flt_stride = 0, flt_cap = 0;
@@ -788,6 +883,7 @@ struct Table {
       (void)hipFree(ctr);
     }
     if (h_ctr) (void)hipHostFree(h_ctr);
+    if (d_scale) (void)hipFree(d_scale);
   }
 
   void init(const mhte_table_config& c, int dev) {
@@ -803,6 +899,7 @@ struct Table {
                                              std::to_string(kMaxSegments));
     segs.assign(c.segments, c.segments + c.n_segments);
     nseg = c.n_segments;
+    retrievers.assign(nseg, Retriever{});
     dim = 0;
     for (auto& s : segs) {
       if (s.dim_size <= 0) throw Error(MHTE_INVALID_ARGUMENT, "segment dim_size must be > 0");
@@ -1048,6 +1145,35 @@ struct Table {
     finish_pending(st);  // a deferred displacement pass always precedes the next op on the table
     if (n <= 0) return;
     Shape sh = pick_shape(dim, vec_ok && aligned16(out));
+    if (has_retriever) {   // the retrievers' instances, the same two launch forms as below
+      const RetrieverArgs ra = retriever_args(false, 0);
+      const int rt = retriever_instance(false);
+      if (sh.VEC == 4 && n >= 4096) {
+        const uint32_t g = uint32_t(((n + 1) / 2 * sh.G + 511) / 512);
+        TableView v = view;
+        v.trace = trace_region(kTagLookup, g, 512);
+        for_shape(sh, [&](auto g_, auto) {
+          constexpr int G = decltype(g_)::value;
+          auto fn = rt == kRtFakeQuant ? lookup_retrieve_kernel_u<G, kRtFakeQuant>
+                    : (rt == kRtHashNet ? lookup_retrieve_kernel_u<G, kRtHashNet> : lookup_retrieve_kernel_u<G, kRtMixed>);
+          LAUNCH_HOT(kTagLookup, fn, g, 512, st, v, ids, n, n_dev, out, count_hits ? 1 : 0, ra);
+        });
+        HIP_OK(hipGetLastError());
+        return;
+      }
+      const dim3 grid(uint32_t((n * sh.G + 255) / 256));
+      TableView v = view;
+      v.trace = trace_region(kTagLookup, grid.x, 256);
+      for_shape(sh, [&](auto g_, auto v_) {
+        constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+        auto fn = rt == kRtFakeQuant ? lookup_retrieve_kernel<G, V, kRtFakeQuant>
+                  : (rt == kRtHashNet ? lookup_retrieve_kernel<G, V, kRtHashNet>
+                                      : lookup_retrieve_kernel<G, V, kRtMixed>);
+        LAUNCH_HOT(kTagLookup, fn, grid, 256, st, v, ids, n, n_dev, out, count_hits ? 1 : 0, ra);
+      });
+      HIP_OK(hipGetLastError());
+      return;
+    }
     // two ids per lane group, 512-thread workgroups, streaming stores: the fastest shape of the
     // sweep over ids per group x workgroup size x store kind (profiles/r01/f_lookup_sweep.jsonl:
     // 6.9 us for 65 536 ids against 9.4 us for one id per group)
@@ -1115,6 +1241,25 @@ struct Table {
     const int64_t threads = n * sh.G;
     const dim3 grid(uint32_t((threads + 255) / 256));
     uint32_t* pend = pending.p;
+    if constexpr (OP == kOpOptimize) {
+      if (has_hash_net) {   // the retriever's Backward in front of the optimizer (Assign / AssignAdd / Reinitialize write raw)
+        const RetrieverArgs ra = retriever_args(true, a.global_step);
+        const bool one = retriever_instance(true) == kRtHashNet;
+        for_shape(sh, [&](auto g_, auto v_) {
+          constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
+          auto fn = one ? upsert_backward_kernel<G, V, kRtHashNet, false>
+                        : (has_group_opt ? upsert_backward_kernel<G, V, kRtMixed, true>
+                                         : upsert_backward_kernel<G, V, kRtMixed, false>);
+          LAUNCH_HOT(kTagUpsert, fn, grid, 256, st, view, ids, n, n_dev, values, seg_off, seg_pos, a, pend, skp, ra);
+        });
+        auto slow = sh.VEC == 4 ? (one ? slowpath_backward_kernel<4, kRtHashNet> : slowpath_backward_kernel<4, kRtMixed>)
+                                : (one ? slowpath_backward_kernel<1, kRtHashNet> : slowpath_backward_kernel<1, kRtMixed>);
+        slow<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, pend, skp, ra);
+        if (a.filter_mode) filter_maintain(st, uint64_t(n));
+        HIP_OK(hipGetLastError());
+        return;
+      }
+    }
     for_shape(sh, [&](auto g_, auto v_) {
       constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
       LAUNCH_HOT(kTagUpsert, (upsert_instance<G, V, OP>(has_group_opt)), grid, 256, st, view, ids, n, n_dev,
@@ -1159,6 +1304,7 @@ struct Table {
   // the fused step kernels take every per-element optimizer (their FULL instantiations beyond SGD /
   // Adagrad / FTRL); the whole-segment GroupAdaGrad stays on the op-level kernels
   bool fusable() const {
+    if (has_retriever) return false;   // (the step kernels read rows raw)
     for (uint32_t i = 0; i < nseg; ++i)
       if (view.seg[i].opt == kOptGroupAdagrad) return false;
     return fusable_shape();
@@ -1713,6 +1859,7 @@ struct mhte_multi_table {
   std::vector<std::unique_ptr<mhte::Table>> tables;  // sorted by name
   // device copies of the tables' views, read by the multi-table launches (mhte_mstep_host.h)
   mhte::DevBuf<mhte::TableView> d_views;
+  mhte::DevBuf<mhte::RetrieverArgs> d_rets;   // the tables' retriever descriptors of a fused-op launch (sync_retrievers)
   std::vector<uint64_t> view_uploaded;
   // the attached touched-key set (mhte_touched_host.h); read under a table's mutex, written under all
   mhte_touched_key_set* touched = nullptr;
@@ -4394,6 +4541,7 @@ mhte_status mhte_table_step_forward(mhte_multi_table* t, int32_t table, const in
   return guard([&] {
     HostProfScope hps(0);
     Table& tb = table_at(t, table);
+    tb.refuse_retriever("step_forward");
     if (!tb.fusable())
       throw Error(MHTE_INVALID_ARGUMENT, "step_forward: row too wide for the fused step");
     HIP_OK(hipSetDevice(t->device));
@@ -4442,6 +4590,7 @@ mhte_status mhte_table_step_backward_ahead(mhte_multi_table* t, int32_t table, m
     // (the lock first: the refusal below reads the attachment, and does not depend on the batch)
     std::lock_guard<std::mutex> g(tb.mu);
     hps.locked();
+    tb.refuse_retriever("step_backward");
     if (t->touched && tb.flt_slots)
       throw Error(MHTE_INVALID_ARGUMENT, "step_backward: a table with an admission filter AND a touched-key set "
                                          "takes the op-level update (mhte_table_sum_optimize_n): the fused step "
@@ -4493,6 +4642,50 @@ mhte_status mhte_table_finish_pending(mhte_multi_table* t, int32_t table, void* 
 int32_t mhte_table_fused_backward_ok(const mhte_multi_table* t, int32_t i) {
   if (!(t && i >= 0 && i < int32_t(t->tables.size()) && t->tables[i]->fusable())) return 0;
   return t->tables[i]->basic_opts() ? 1 : 2;
+}
+
+mhte_status mhte_table_set_retriever(mhte_multi_table* t, int32_t table, int32_t segment, int32_t type,
+                                     const float* params, int32_t n_params) {
+  return guard([&] {
+    Table& tb = table_at(t, table);
+    HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> link(g_touched_link_mu);   // (before the table's, as everywhere: the step lists)
+    std::lock_guard<std::mutex> g(tb.mu);
+    if (type != MHTE_RETRIEVER_RAW && (!t->multi_steps.empty() || !t->shard_steps.empty()))
+      throw Error(MHTE_FAILED_PRECONDITION, "set_retriever: a multi-table or id-sharded step exists on this "
+                                            "MultiHashTable; its kernels read rows raw");
+    tb.set_retriever(segment, type, params, n_params);
+  });
+}
+
+mhte_status mhte_table_get_retriever(mhte_multi_table* t, int32_t table, int32_t segment, int32_t* type,
+                                     float* params, int32_t cap) {
+  return guard([&] {
+    Table& tb = table_at(t, table);
+    if (segment < 0 || segment >= int32_t(tb.nseg) || !type)
+      throw Error(MHTE_INVALID_ARGUMENT, "get_retriever: bad segment or null argument");
+    std::lock_guard<std::mutex> g(tb.mu);
+    const Table::Retriever& r = tb.retrievers[segment];
+    *type = r.type;
+    const int32_t np = r.type == kRetFakeQuant ? 1 : (r.type == kRetHashNet ? 4 : 0);
+    for (int32_t i = 0; params && i < np && i < cap; ++i) params[i] = r.p[i];
+  });
+}
+
+mhte_status mhte_table_hash_net_scale(mhte_multi_table* t, int32_t table, int32_t segment, float* host_out,
+                                      void* stream) {
+  return guard([&] {
+    Table& tb = table_at(t, table);
+    if (!host_out) throw Error(MHTE_INVALID_ARGUMENT, "hash_net_scale: null argument");
+    HIP_OK(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> g(tb.mu);
+    if (segment < 0 || segment >= int32_t(tb.nseg) || tb.retrievers[segment].type != kRetHashNet)
+      throw Error(MHTE_INVALID_ARGUMENT, "hash_net_scale: table " + tb.name + " segment " +
+                                             std::to_string(segment) + " has no hash_net retriever");
+    tb.finish_pending(S(stream));
+    HIP_OK(hipMemcpyAsync(host_out, tb.d_scale + segment, sizeof(float), hipMemcpyDeviceToHost, S(stream)));
+    HIP_OK(hipStreamSynchronize(S(stream)));
+  });
 }
 
 mhte_status mhte_value_offsets(const uint32_t* seg_off, const uint32_t* seg_pos,
@@ -5107,6 +5300,19 @@ mhte_status mhte_multi_table_create_from_proto(const void* config, int64_t confi
       return st;
     }
   }
+  // comp_config -> the segments' retrievers (GenerateObjFromSegments, entry_accessor.cc:283-302)
+  for (const auto& t : tabs)
+    for (size_t k = 0; k < t.segs.size(); ++k) {
+      const pcfg::Segment& s = t.segs[k];
+      if (s.retriever == MHTE_RETRIEVER_RAW) continue;
+      st = mhte_table_set_retriever(*out, mhte_table_index(*out, t.name.c_str()), int32_t(k), s.retriever,
+                                    s.retriever_params, s.retriever == MHTE_RETRIEVER_HASH_NET ? 4 : 1);
+      if (st != MHTE_OK) {
+        mhte_multi_table_destroy(*out);
+        *out = nullptr;
+        return st;
+      }
+    }
   if (learning_rates_out) {  // sorted-name order, like the tables
     int32_t k = 0;
     for (auto& tb : (*out)->tables)
@@ -5369,6 +5575,7 @@ mhte_status mhte_multi_step_create(mhte_multi_table* t, int64_t max_batch_per_ta
     std::lock_guard<std::mutex> link(g_touched_link_mu);   // (before the tables', as everywhere)
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto& tb : t->tables) locks.emplace_back(tb->mu);
+    for (auto& tb : t->tables) tb->refuse_retriever("multi step");
     if (t->touched && tk_any_filter(t))
       throw Error(MHTE_INVALID_ARGUMENT, "multi step: a MultiHashTable with an admission filter AND a touched-key "
                                          "set takes the op-level update: the fused step decides admission inside "

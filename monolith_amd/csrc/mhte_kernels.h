@@ -11,6 +11,7 @@
 #define MHTE_KERNELS_H_
 
 #include "mhte_core.h"
+#include "mhte_qat_kernels.h"
 
 // Development builds (-DMHTE_DEV_FAST, scripts/dev_build.sh) instantiate the device-side lane-group
 // switches for G = 16 only (dim 64): the other cases do nothing.
@@ -650,11 +651,14 @@ __global__ __launch_bounds__(256) void filter_clear_kernel(TableView tv) {
 // (cuckoo_embedding_hash_table.cc:161-171).  Algorithmic bytes per id: 8 (id) + 36..72 (probe)
 // + 4*dim (row) + 4*dim (output).
 // =============================================================================================
-template <int G, int VEC>
+// RT (RetrieverInstance, mhte_qat_kernels.h): a table with a non-raw segment retriever has the
+// retriever applied to a resident row's weights in registers, between the load and the store; `ra`:
+// its descriptors.  A miss stays zeros (both transforms map 0 to 0).
+template <int G, int VEC, int RT = kRtRaw>
 __device__ __forceinline__ void lookup_role(const TableView& tv, const int64_t* __restrict__ ids,
                                             int64_t n, const uint32_t* __restrict__ n_dev,
                                             float* __restrict__ out, int count_hits, uint32_t bid,
-                                            int gate = 0) {
+                                            int gate = 0, const RetrieverArgs* ra = nullptr) {
   const int lane = threadIdx.x & 63;
   const int j = lane & (G - 1);
   const int gbase = lane & ~(G - 1);
@@ -700,6 +704,7 @@ __device__ __forceinline__ void lookup_role(const TableView& tv, const int64_t* 
       Vec<VEC> v;
       if (found) {
         v.load(rp + e);
+        if constexpr (RT != kRtRaw) retrieve_lane<RT, VEC>(v.v, e, *ra);
       } else {
 #pragma unroll
         for (int c = 0; c < VEC; ++c) v.v[c] = 0.f;
@@ -741,11 +746,13 @@ __device__ __forceinline__ void store_out_rows(float* p, const Vec<VEC>& v) {
   }
 }
 // NT: 0 plain stores, 1 streaming (nontemporal), 2 write-through (store_out_rows)
-template <int G, int VEC, int UNR, int NT>
+// RT / ra: the segment retrievers, as in lookup_role
+template <int G, int VEC, int UNR, int NT, int RT = kRtRaw>
 __device__ __forceinline__ void lookup_role_u(const TableView& tv, const int64_t* __restrict__ ids,
                                               int64_t n, const uint32_t* __restrict__ n_dev,
                                               float* __restrict__ out, int count_hits,
-                                              int64_t group, const int64_t* pre = nullptr) {
+                                              int64_t group, const int64_t* pre = nullptr,
+                                              const RetrieverArgs* ra = nullptr) {
   const int lane = threadIdx.x & 63;
   const int j = lane & (G - 1);
   const int gbase = lane & ~(G - 1);
@@ -802,6 +809,7 @@ __device__ __forceinline__ void lookup_role_u(const TableView& tv, const int64_t
     for (int u = 0; u < UNR; ++u) {
       if (found[u]) {
         v[u].load(rp[u] + e);
+        if constexpr (RT != kRtRaw) retrieve_lane<RT, VEC>(v[u].v, e, *ra);
       } else {
 #pragma unroll
         for (int c = 0; c < VEC; ++c) v[u].v[c] = 0.f;
@@ -831,12 +839,34 @@ __global__ __launch_bounds__(BLOCK) void lookup_kernel_u(TableView tv,
   wt.end(5u);
 }
 
+// ... of a table with segment retrievers (two ids per lane group, streaming stores)
+template <int G, int RT>
+__global__ __launch_bounds__(512) void lookup_retrieve_kernel_u(TableView tv, const int64_t* __restrict__ ids,
+                                                                int64_t n, const uint32_t* __restrict__ n_dev,
+                                                                float* __restrict__ out, int count_hits,
+                                                                RetrieverArgs ra) {
+  WaveTrace wt(tv.trace);
+  lookup_role_u<G, 4, 2, 1, RT>(tv, ids, n, n_dev, out, count_hits, (int64_t(blockIdx.x) * 512 + threadIdx.x) / G,
+                                nullptr, &ra);
+  wt.end(5u);
+}
+
 template <int G, int VEC>
 __global__ __launch_bounds__(256) void lookup_kernel(TableView tv, const int64_t* __restrict__ ids,
                                                      int64_t n, const uint32_t* __restrict__ n_dev,
                                                      float* __restrict__ out, int count_hits) {
   WaveTrace wt(tv.trace);
   lookup_role<G, VEC>(tv, ids, n, n_dev, out, count_hits, blockIdx.x);
+  wt.end(5u);
+}
+// ... of a table with segment retrievers: the same role, the retrievers applied on the way
+template <int G, int VEC, int RT>
+__global__ __launch_bounds__(256) void lookup_retrieve_kernel(TableView tv, const int64_t* __restrict__ ids,
+                                                              int64_t n, const uint32_t* __restrict__ n_dev,
+                                                              float* __restrict__ out, int count_hits,
+                                                              RetrieverArgs ra) {
+  WaveTrace wt(tv.trace);
+  lookup_role<G, VEC, RT>(tv, ids, n, n_dev, out, count_hits, blockIdx.x, 0, &ra);
   wt.end(5u);
 }
 
@@ -986,11 +1016,16 @@ __device__ __forceinline__ void group_adagrad_segment(const TableView& tv, float
 // GROUP = false: the table has no GroupAdaGrad segment (the host picks the instantiation): the
 // whole-segment pass is compiled out — with it, the compiler keeps the table descriptor in scratch
 // memory and every other optimizer's update runs three times slower.
-template <int G, int VEC, int OP, bool BASIC = false, bool GROUP = true>
+// RT (RetrieverInstance): a table with a HashNet segment has the retriever's Backward applied to
+// each gradient handed to the optimizer — every occurrence's, or the sum's where duplicates are
+// summed — at the weights the lane holds at that moment: the initializer's for a new id, the ones
+// the previous occurrence left for a sequential duplicate.
+template <int G, int VEC, int OP, bool BASIC = false, bool GROUP = true, int RT = kRtRaw>
 __device__ __forceinline__ void apply_row(const TableView& tv, float* rp, bool is_new, int j,
                                           const float* __restrict__ values,
                                           const uint32_t* __restrict__ seg_pos, uint32_t q0,
-                                          uint32_t q1, int64_t self_pos, const ApplyArgs& a) {
+                                          uint32_t q1, int64_t self_pos, const ApplyArgs& a,
+                                          const RetrieverArgs* ra = nullptr) {
   const int64_t dim = tv.dim;
   if (OP == kOpOptimize && !BASIC && GROUP) {  // (group-uniform: every lane walks the segments)
     for (uint32_t k = 0; k < tv.nseg; ++k)
@@ -1058,6 +1093,7 @@ __device__ __forceinline__ void apply_row(const TableView& tv, float* rp, bool i
           if (t + 1 < nq) continue;
           v = acc;
         }
+        if constexpr (RT != kRtRaw && OP == kOpOptimize) backward_lane<RT, VEC>(v.v, w.v, e, *ra);
         const float lr_eff = scal ? adam_lr(lr, c1, c2) : lr;
         // (the AVX form of Adagrad is decided once per row, not per element: a branch per element
         // took the segment kernels from 128 to 131 VGPRs = 4 -> 3 wavefronts per SIMD)
@@ -1123,7 +1159,10 @@ __device__ __forceinline__ void apply_row(const TableView& tv, float* rp, bool i
       if (nv > 0) s1.store(st1);
       if (nv > 1) s2.store(st2);
       if (nv > 2) s3.store(st3);
-      if (scal && le == 0) {  // (every lane of the segment computed the same powers)
+      // (every lane of the segment computed the same powers.  The lane of the segment's LAST chunk writes
+      // them: a group walks a row of more than G * VEC floats in several rounds, and a store in an earlier
+      // round — the first chunk's — was read back as the powers of the columns of the later rounds)
+      if (scal && le + uint32_t(VEC) >= uint32_t(sd.dim)) {
         sc[0] = c1;
         sc[1] = c2;
         sc[2] = 0.f;
@@ -1142,6 +1181,9 @@ __device__ __forceinline__ void apply_row(const TableView& tv, float* rp, bool i
         sc[3] = 0.f;
       }
     }
+  }
+  if constexpr (RT != kRtRaw && OP == kOpOptimize) {
+    if (j == 0) hash_net_store_scales(*ra);
   }
 }
 
@@ -1341,6 +1383,61 @@ __global__ __launch_bounds__(256) void upsert_kernel(TableView tv, const int64_t
       }
     }
   }
+}
+
+// The Optimize of a table with a HashNet segment (RT: kRtHashNet, the one-segment table; kRtMixed):
+// upsert_kernel's steps, the retriever's Backward in the row update (apply_row), its descriptors a
+// kernel argument of this instance alone.
+// KEEP IN STEP with upsert_kernel: the probe, the admission filter and the defer step below are copies
+// of its own (the raw kernel's source and arguments were not to change); a change there belongs here too.
+template <int G, int VEC, int RT, bool GROUP>
+__global__ __launch_bounds__(256) void upsert_backward_kernel(TableView tv, const int64_t* __restrict__ ids,
+                                                              int64_t n, const uint32_t* __restrict__ n_dev,
+                                                              const float* __restrict__ values,
+                                                              const uint32_t* __restrict__ seg_off,
+                                                              const uint32_t* __restrict__ seg_pos,
+                                                              ApplyArgs a, uint32_t* __restrict__ pending,
+                                                              uint32_t* __restrict__ skip, RetrieverArgs ra) {
+  const int lane = threadIdx.x & 63;
+  const int j = lane & (G - 1);
+  const int64_t g = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;
+  if (n_dev) n = min(n, int64_t(*n_dev));
+  bool valid = g < n;
+  const int64_t id = valid ? ids[g] : 0;
+  const uint64_t hv = hash_key(id);
+  const uint64_t i1 = index_hash(tv.hp, hv);
+  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1);
+  Bucket* b = assume_global(tv.buckets + ((j < 4) ? i1 : i2));
+  int64_t k = kEmptyKey;
+  uint32_t row = kNoRow;
+  if (valid && id != kEmptyKey && j < 8) {
+    k = b->key[j & 3];
+    row = b->row[j & 3];
+  }
+  uint32_t q0 = (valid && seg_off) ? seg_off[g] : 0u;
+  const uint32_t q1 = (valid && seg_off) ? seg_off[g + 1] : 1u;
+  if (tv.flt_slots && a.filter_mode) {   // admission: an id whose occurrences are all dropped has no Backward
+    const int gbase = lane & ~(G - 1);
+    bool contained = group_mask_of<G>(__ballot(valid && id != kEmptyKey && j < 8 && k == id), gbase) != 0;
+    if (valid && id == kEmptyKey) contained = tv.ctr->special_state == 1;
+    uint32_t first = 0;
+    if (valid && j == 0) {
+      const int mode = (a.filter_mode == 1 && a.sum_dups) ? 2 : a.filter_mode;
+      first = filter_consult(tv, id, q1 - q0, mode, contained);
+    }
+    first = __shfl(first, gbase);
+    if (first >= q1 - q0) valid = false;
+    q0 += first;
+  }
+  const SlotResult sr = upsert_resolve<G>(tv, b, id, valid, k, row, lane, a.ts);
+  if (sr.deferred && j == 0) {
+    const uint32_t slot = atomicAdd(&tv.ctr->n_pending, 1u);
+    pending[slot] = static_cast<uint32_t>(g);
+    if (skip) skip[g] = q0;
+  }
+  if (valid && !sr.deferred)
+    apply_row<G, VEC, kOpOptimize, false, GROUP, RT>(tv, row_ptr(tv, sr.r), sr.is_new, j, values,
+                                                     seg_off ? seg_pos : nullptr, q0, q1, g, a, &ra);
 }
 
 // =============================================================================================
@@ -1588,7 +1685,7 @@ __device__ __forceinline__ void slow_pass_done(const TableView& tv, int lane) {
 // The single-table pass: ids[pending[i]] (one word per entry), one entry or the id's occurrence
 // list, or a reinit with its status.  GATED: inside step_fwd_kernel (slow_pass_done).
 // BASIC (gated launches = the fused step kernels): the update code of SGD / Adagrad / FTRL only.
-template <int VEC, int OP, bool SOLO, bool GATED = false, bool BASIC = GATED>
+template <int VEC, int OP, bool SOLO, bool GATED = false, bool BASIC = GATED, int RT = kRtRaw>
 __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t* __restrict__ ids,
                                               const float* __restrict__ values,
                                               const uint32_t* __restrict__ seg_off,
@@ -1596,7 +1693,8 @@ __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t
                                               const ApplyArgs& a, int32_t* __restrict__ status,
                                               const uint32_t* __restrict__ pending,
                                               BfsSlot* q, CuckooRecord* path,
-                                              const uint32_t* __restrict__ skip = nullptr) {
+                                              const uint32_t* __restrict__ skip = nullptr,
+                                              const RetrieverArgs* ra = nullptr) {
   const int lane = threadIdx.x;
   // (the count and the first entry of the list are fetched together: the other workgroups of a
   // gated launch wait for this pass, every dependent round trip in it is paid by all of them)
@@ -1610,8 +1708,8 @@ __device__ __forceinline__ void slowpath_role(const TableView& tv, const int64_t
       // (skip: first occurrence the admission filter let through, upsert_kernel)
       const uint32_t q0 = (skip && seg_off) ? skip[g] : (seg_off ? seg_off[g] : 0u);
       const uint32_t q1 = seg_off ? seg_off[g + 1] : 1u;
-      apply_row<64, VEC, OP, BASIC, (GATED ? false : true)>(tv, row_ptr(tv, pl.r), true, lane, values,
-                                                            seg_off ? seg_pos : nullptr, q0, q1, g, a);
+      apply_row<64, VEC, OP, BASIC, (GATED ? false : true), RT>(tv, row_ptr(tv, pl.r), true, lane, values,
+                                                                seg_off ? seg_pos : nullptr, q0, q1, g, a, ra);
       if (OP == kOpReinit && lane == 0) {
         if (seg_off) {
           for (uint32_t t = q0; t < q1; ++t) status[seg_pos[t]] = (t == q0) ? 0 : 1;
@@ -1789,6 +1887,20 @@ __global__ __launch_bounds__(64) void slowpath_kernel(TableView tv, const int64_
   __shared__ BfsSlot q[kMaxCuckooCount];
   __shared__ CuckooRecord path[kMaxBfsPathLen];
   slowpath_role<VEC, OP, true>(tv, ids, values, seg_off, seg_pos, a, status, pending, q, path, skip);
+}
+// ... of an Optimize on a table with a HashNet segment
+template <int VEC, int RT>
+__global__ __launch_bounds__(64) void slowpath_backward_kernel(TableView tv, const int64_t* __restrict__ ids,
+                                                               const float* __restrict__ values,
+                                                               const uint32_t* __restrict__ seg_off,
+                                                               const uint32_t* __restrict__ seg_pos,
+                                                               ApplyArgs a, const uint32_t* __restrict__ pending,
+                                                               const uint32_t* __restrict__ skip,
+                                                               RetrieverArgs ra) {
+  __shared__ BfsSlot q[kMaxCuckooCount];
+  __shared__ CuckooRecord path[kMaxBfsPathLen];
+  slowpath_role<VEC, kOpOptimize, true, false, false, RT>(tv, ids, values, seg_off, seg_pos, a, nullptr, pending,
+                                                          q, path, skip, &ra);
 }
 
 

@@ -163,6 +163,8 @@ struct MultiStep {
     if (mb <= 0 || mb > int64_t(kRdMaxBlocks) * kRdBlock)
       throw Error(MHTE_INVALID_ARGUMENT, "multi step: max batch per table must be 1.." +
                                              std::to_string(kRdMaxBlocks * kRdBlock));
+    // (a check of its own, for the id-sharded step's sender roles too: its owner side reads rows raw as well)
+    for (uint32_t t = 0; t < T; ++t) m->tables[t]->refuse_retriever(sender_roles_only ? "shard step" : "multi step");
     for (uint32_t t = 0; t < T; ++t) {
       const Table& tb = *m->tables[t];
       if (!tb.fusable() && !(sender_roles_only && tb.fusable_shape()))
@@ -723,11 +725,28 @@ static bool seg_kernels_ok(const mhte_multi_table* t) {
   return t->tables.size() <= size_t(kMaxStepTables) && seg_shapes_ok(t);
 }
 
+// The retriever descriptors of every table in device memory for the retriever instances of the segment
+// kernels (update: with the call's candidate scales); stream-ordered behind the launches that read the
+// previous ones.  -> false: no table of the kind (lookups: any retriever; updates: a HashNet segment).
+static bool sync_retrievers(mhte_multi_table* t, bool update, int64_t global_step, hipStream_t st) {
+  bool any = false;
+  for (auto& tb : t->tables) any = any || (update ? tb->has_hash_net : tb->has_retriever);
+  if (!any) return false;
+  const size_t T = t->tables.size();
+  std::vector<RetrieverArgs> h(T);
+  for (size_t k = 0; k < T; ++k) h[k] = t->tables[k]->retriever_args(update, global_step);
+  t->d_rets.reserve(T);
+  HIP_OK(hipMemcpyAsync(t->d_rets.p, h.data(), sizeof(RetrieverArgs) * T, hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));   // (the source is this call's own; retriever tables only)
+  return true;
+}
+
 static void fused_lookup_segments(mhte_multi_table* t, const int64_t* ids, const int32_t* ko,
                                   const int32_t* eo, int nseg_all, float* embeddings, hipStream_t st) {
   const int T = int(t->tables.size());
   for (auto& tb : t->tables) tb->finish_pending(st);
   sync_views(t, st);
+  const bool rets = sync_retrievers(t, false, 0, st);
   const int per = std::max(T, (kMaxSegs / T) * T);  // whole shards per launch
   for (int s0 = 0; s0 < nseg_all; s0 += per) {
     const int ns = std::min(per, nseg_all - s0);
@@ -756,10 +775,21 @@ static void fused_lookup_segments(mhte_multi_table* t, const int64_t* ids, const
       gx = std::max(gx, uint32_t((uint64_t((n + 1) / 2) * g + 511) / 512));
     }
     if (gx == 0) continue;
-    bool w4 = false, w1 = false;
-    for (int k = 0; k < T; ++k) ((A.g[k] & 1u) ? w1 : w4) = true;
+    bool w4 = false, w1 = false, r4 = false, r1 = false;   // raw / retriever tables per lane width
+    for (int k = 0; k < T; ++k) {
+      if (t->tables[k]->has_retriever) {
+        ((A.g[k] & 1u) ? r1 : r4) = true;
+        A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
+      } else {
+        ((A.g[k] & 1u) ? w1 : w4) = true;
+      }
+    }
     if (w4) LAUNCH_HOT(kTagLookup, seg_lookup_kernel<4>, dim3(gx, ns), 512, st, A);
     if (w1) LAUNCH_HOT(kTagLookup, seg_lookup_kernel<1>, dim3(gx, ns), 512, st, A);
+    if (rets && r4)
+      LAUNCH_HOT(kTagLookup, seg_lookup_retrieve_kernel<4>, dim3(gx, ns), 512, st, A, ConstRetrievers(t->d_rets.p));
+    if (rets && r1)
+      LAUNCH_HOT(kTagLookup, seg_lookup_retrieve_kernel<1>, dim3(gx, ns), 512, st, A, ConstRetrievers(t->d_rets.p));
     HIP_OK(hipGetLastError());
   }
 }
@@ -784,6 +814,10 @@ static void fused_optimize_segments(mhte_multi_table* t, const int64_t* ids,
     tb.pending.reserve(2 * size_t(per_table[size_t(k)]) + 2);
   }
   sync_views(t, st);
+  // (a call without ids runs no Backward: the HashNet scales stay)
+  uint64_t n_all = 0;
+  for (int k = 0; k < T; ++k) n_all += per_table[size_t(k)];
+  const bool rets = n_all != 0 && sync_retrievers(t, true, global_step, st);
   const int per = std::max(T, (kMaxSegs / T) * T);
   for (int s0 = 0; s0 < nseg_all; s0 += per) {
     const int ns = std::min(per, nseg_all - s0);
@@ -821,7 +855,21 @@ static void fused_optimize_segments(mhte_multi_table* t, const int64_t* ids,
     if (gx == 0) continue;
     gx = std::min<uint32_t>(gx, 1024);
     bool inst[2][2] = {};   // [one float per lane][whole-segment optimizer]
-    for (int k = 0; k < T; ++k) inst[A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
+    bool rinst[2][2] = {};  // ... of the tables with a HashNet segment
+    for (int k = 0; k < T; ++k) {
+      if (rets && t->tables[k]->has_hash_net) {
+        rinst[A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
+        A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
+      } else {
+        inst[A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
+      }
+    }
+    const ConstRetrievers R = ConstRetrievers(t->d_rets.p);
+    if (rinst[0][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<4, false>), dim3(gx, ns), 256, st, A, R);
+    if (rinst[1][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<1, false>), dim3(gx, ns), 256, st, A, R);
+    if (rinst[0][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<4, true>), dim3(gx, ns), 256, st, A, R);
+    if (rinst[1][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<1, true>), dim3(gx, ns), 256, st, A, R);
+    if (rinst[0][0] || rinst[1][0] || rinst[0][1] || rinst[1][1]) seg_slow_backward_kernel<<<T, 64, 0, st>>>(A, R);
     if (inst[0][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<4, false>), dim3(gx, ns), 256, st, A);
     if (inst[1][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<1, false>), dim3(gx, ns), 256, st, A);
     if (inst[0][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<4, true>), dim3(gx, ns), 256, st, A);

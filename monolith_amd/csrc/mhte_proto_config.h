@@ -6,6 +6,7 @@
 //   SlotExpireTimeConfig            :54-64    SlotOccurrenceThresholdConfig :100-110
 //   OptimizerConfig and the per-optimizer configs   RT/hash_table/optimizer/optimizer.proto
 //   InitializerConfig               RT/hash_table/initializer/initializer_config.proto
+//   FloatCompressorConfig           RT/hash_table/compressor/float_compressor.proto
 // Hand-written protobuf wire decoding (no protobuf runtime in the engine); field numbers and
 // defaults restated from the .proto files.  Host-only, included by mhte.hip.
 #ifndef MHTE_PROTO_CONFIG_H_
@@ -88,6 +89,10 @@ inline float f32_of(const Field& f) {
 struct Segment {
   mhte_segment_config c;
   float learning_rate;   // the config's own (the ops take the live value as an input)
+  // comp_config -> the segment's retriever (entry_accessor.cc:283-302): MHTE_RETRIEVER_* and the
+  // parameters of mhte_table_set_retriever
+  int32_t retriever;
+  float retriever_params[4];
 };
 struct TableCfg {
   std::string name;
@@ -227,6 +232,46 @@ inline void parse_initializer(const uint8_t* b, size_t n, Segment* s) {
   }
 }
 
+// FloatCompressorConfig (float_compressor.proto:19-50): the oneof arm picks the TRAINING retriever —
+// fp32 (1) / fp16 (2): raw; fixed_r8 (3): fake quant, r (2) default 1.0; one_bit (4): HashNet,
+// step_size (2, int64) 200, init_scale (3) 1.0, max_scale (4) 10000, amplitude (5) 0.1.  The last arm on
+// the wire wins, as in a oneof.
+inline void parse_compressor(const uint8_t* b, size_t n, Segment* s) {
+  Msg m(b, n);
+  Field f;
+  while (m.next(&f)) {
+    if (f.wt != 2 || f.num < 1 || f.num > 4) continue;
+    Msg o(f.p, f.n);
+    Field g;
+    for (float& p : s->retriever_params) p = 0.f;
+    if (f.num <= 2) {
+      s->retriever = MHTE_RETRIEVER_RAW;
+    } else if (f.num == 3) {
+      s->retriever = MHTE_RETRIEVER_FAKE_QUANT_R8;
+      s->retriever_params[0] = 1.0f;
+      while (o.next(&g))
+        if (g.num == 2) s->retriever_params[0] = f32_of(g);
+    } else {
+      s->retriever = MHTE_RETRIEVER_HASH_NET;
+      int64_t step_size = 200;
+      s->retriever_params[1] = 1.0f;
+      s->retriever_params[2] = 10000.0f;
+      s->retriever_params[3] = 0.1f;
+      while (o.next(&g)) {
+        if (g.num == 2 && g.wt == 0) step_size = int64_t(g.v);
+        if (g.num >= 3 && g.num <= 5) s->retriever_params[g.num - 2] = f32_of(g);
+      }
+      // (global_step % step_size, hash_net_quantizer.h:47: zero divides by zero there)
+      if (step_size <= 0)
+        throw ckpt::ProtoError("config: one_bit compressor with step_size " + std::to_string(step_size) +
+                               " (must be > 0)");
+      if (step_size > (int64_t(1) << 24))
+        throw ckpt::ProtoError("config: one_bit compressor: step_size above 2^24 is not supported");
+      s->retriever_params[0] = float(step_size);
+    }
+  }
+}
+
 inline void parse_table(const uint8_t* b, size_t n, TableCfg* t) {
   Msg m(b, n);
   Field f;
@@ -248,6 +293,7 @@ inline void parse_table(const uint8_t* b, size_t n, TableCfg* t) {
           while (sm.next(&h)) {
             if (h.num == 1 && h.wt == 2) parse_initializer(h.p, h.n, &s);
             else if (h.num == 2 && h.wt == 2) { parse_optimizer(h.p, h.n, &s); has_opt = true; }
+            else if (h.num == 3 && h.wt == 2) parse_compressor(h.p, h.n, &s);
             else if (h.num == 7 && h.wt == 0) s.c.dim_size = int32_t(h.v);
           }
           if (!has_opt) throw ckpt::ProtoError("config: segment without opt_config");

@@ -295,6 +295,7 @@ struct ShardStep {
     world = world_;
     max_batch = mb;
     T = uint32_t(m->tables.size());
+    for (auto& tb : m->tables) tb->refuse_retriever("shard step");
     if (world < 1 || world > kMaxShards || rank < 0 || rank >= world)
       throw Error(MHTE_INVALID_ARGUMENT, "shard step: rank / world out of range (world <= " +
                                              std::to_string(kMaxShards) + ")");

@@ -244,9 +244,48 @@ class RandomUniformInitializer(Initializer):
     self.value2 = float(maxval)
 
 
-class Fp32Compressor:
-  """reference entry.py:505-511 — training rows are fp32; the serving-side compressors are out of
-  scope."""
+class Compressor:
+  """reference entry.py:458-463.  Rows of a TRAINING table are fp32 whatever the compressor (compressed
+  storage is the SERVING entries', out of scope: SURVEY.md §2 row 4); what a compressor decides here is
+  the segment's retriever (entry_accessor.cc:283-302): ``retriever()`` -> (MHTE_RETRIEVER_*, params of
+  mhte_table_set_retriever)."""
+
+  def retriever(self):
+    return _lib.MHTE_RETRIEVER_RAW, ()
+
+
+class OneBitCompressor(Compressor):
+  """reference entry.py:467-478 (HashNet): lookups return amplitude * tanh(scale * w), the update scales
+  the gradient by the derivative first, scale grows with global_step every ``step_size`` steps.
+  init_scale 1.0 and max_scale 10000 are the proto's defaults (float_compressor.proto:36-42), which the
+  reference's Python class leaves unset."""
+
+  def __init__(self, step_size: int = 200, amplitude: float = 0.05):
+    self.step_size = int(step_size)
+    self.amplitude = float(amplitude)
+
+  def retriever(self):
+    return _lib.MHTE_RETRIEVER_HASH_NET, (float(self.step_size), 1.0, 10000.0, self.amplitude)
+
+
+class FixedR8Compressor(Compressor):
+  """reference entry.py:482-491 ("qat8"): lookups return the weight quantized to 256 slots of width
+  fixed_range / 128."""
+
+  def __init__(self, fixed_range=1.0):
+    self.r = float(fixed_range)
+
+  def retriever(self):
+    return _lib.MHTE_RETRIEVER_FAKE_QUANT_R8, (self.r,)
+
+
+class Fp16Compressor(Compressor):
+  """reference entry.py:495-501 — FeatureSlot's default; encodes SERVING entries only, the raw retriever
+  in training."""
+
+
+class Fp32Compressor(Compressor):
+  """reference entry.py:505-511"""
 
 
 @dataclasses.dataclass
@@ -255,18 +294,21 @@ class Segment:
   dim_size: int
   initializer: Initializer
   optimizer: Optimizer
+  compressor: Optional[Compressor] = None
 
 
 def CombineAsSegment(dim_size: int, initializer: Initializer, optimizer: Optimizer,
                      compressor: Any = None) -> Segment:
   """reference entry.py:514-537"""
-  if compressor is not None and not isinstance(compressor, Fp32Compressor):
-    raise NotImplementedError("only Fp32Compressor rows are on the MI355X hot path")
+  if compressor is not None and type(compressor) not in (Fp32Compressor, Fp16Compressor, FixedR8Compressor,
+                                                         OneBitCompressor):
+    raise NotImplementedError("compressor %r is not supported (Fp32Compressor, Fp16Compressor, "
+                              "FixedR8Compressor, OneBitCompressor)" % (compressor,))
   if not isinstance(initializer, Initializer) or initializer.init_type is None:
     raise NotImplementedError("initializer %r is not supported" % (initializer,))
   if not isinstance(optimizer, Optimizer) or optimizer.opt_type is None:
     raise NotImplementedError("optimizer %r is not supported" % (optimizer,))
-  return Segment(dim_size=int(dim_size), initializer=initializer, optimizer=optimizer)
+  return Segment(dim_size=int(dim_size), initializer=initializer, optimizer=optimizer, compressor=compressor)
 
 
 @dataclasses.dataclass

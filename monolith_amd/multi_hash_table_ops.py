@@ -216,8 +216,24 @@ class MultiHashTable:
     MultiHashTable._names_in_use.add(self._shared_name)
     self._slice_sizes = tuple(
         self._lib.mhte_table_slice_size(self._h, i) for i in range(len(self._table_names)))
+    try:
+      self._set_retrievers(configs)
+    except Exception:
+      self.close()
+      raise
     # Feature eviction (tf_bridge.cc:73-104) lives behind the boundary: the library checks the
     # cadence on its update entry points and enqueues the scan on their stream.
+
+  def _set_retrievers(self, configs):
+    """The segments' compressors -> their retrievers (entry_accessor.cc:283-302), after creation: the
+    retriever does not ride in mhte_segment_config."""
+    for i, n in enumerate(self._table_names):
+      for k, s in enumerate(configs[n].table_config.segments):
+        comp = getattr(s, "compressor", None)
+        rtype, params = comp.retriever() if comp is not None else (_lib.MHTE_RETRIEVER_RAW, ())
+        if rtype != _lib.MHTE_RETRIEVER_RAW:
+          arr = (C.c_float * len(params))(*params)
+          check(self._lib.mhte_table_set_retriever(self._h, i, k, rtype, arr, len(params)))
 
   @classmethod
   def from_configs(cls, configs: Dict[str, entry.HashTableConfigInstance], *args, **kwargs):
@@ -554,6 +570,24 @@ class MultiHashTable:
     if i < 0:
       raise KeyError(name)
     return i
+
+  def retrievers(self, name: str) -> List[Tuple[int, Tuple[float, ...]]]:
+    """[(MHTE_RETRIEVER_*, params)] of the table's segments (mhte_table_get_retriever): () for the raw
+    retriever, (r,) for fake quant, (step_size, init_scale, max_scale, amplitude) for HashNet."""
+    i = self._index(name)
+    out = []
+    for k in range(self._slice_sizes[i]):
+      rtype, params = (C.c_int32 * 1)(), (C.c_float * 4)()
+      check(self._lib.mhte_table_get_retriever(self._h, i, k, rtype, params, 4))
+      np_ = {_lib.MHTE_RETRIEVER_FAKE_QUANT_R8: 1, _lib.MHTE_RETRIEVER_HASH_NET: 4}.get(rtype[0], 0)
+      out.append((int(rtype[0]), tuple(float(params[j]) for j in range(np_))))
+    return out
+
+  def hash_net_scale(self, name: str, segment: int = 0) -> float:
+    """The live scale of a HashNet segment (mhte_table_hash_net_scale); synchronises."""
+    v = (C.c_float * 1)()
+    check(self._lib.mhte_table_hash_net_scale(self._h, self._index(name), int(segment), v, _stream()))
+    return float(v[0])
 
   def size(self, name: str) -> int:
     n = (C.c_int64 * 1)()
