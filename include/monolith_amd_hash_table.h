@@ -402,6 +402,43 @@ mhte_status mhte_clip_by_global_norm_fused(const float* const* inputs, float* co
 mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* outputs, const int64_t* lens,
                                    int32_t n, const float* scale_dev, void* stream);
 
+/* ---- aligned flat concat / split (csrc/mhte_flat_kernels.h) ----------------------------------------
+ * MonolithAlignedFlatConcat and MonolithAlignedFlatSplit (RT/ops/aligned_concat_split.cu.cc:32-57, :63-128)
+ * with the layout rule of FusedAlignedOutputAllocator (RT/ops/alloc_utils.h:50-95): the allreduce side of
+ * the deferred clip (NT/feature_utils.py:48-99 allreduce_cond with fusion 'one', :251-264 cond_defer_clip).
+ *   inputs        HOST array of n device pointers (fp32); lens HOST [n], floats per tensor (0 is legal: the
+ *                 tensor occupies nothing and its pointer is not looked at)
+ *   align_elems   A, the alignment of every tensor's start in ELEMENTS: a power of two in [4, 1024]
+ *                 (the reference's is EIGEN_MAX_ALIGN_BYTES / sizeof(float) of its build: 16 for 64 bytes)
+ *   offsets       HOST [n + 1]: offsets[i] = the sum of round_up(lens[j], A) over j < i; offsets[n] the total
+ *   out           [dev, out_elems] fp32 (wire 0) or fp16 (wire 1), 16-byte aligned; out_elems == offsets[n]
+ * out[offsets[i] + k] = in[i][k] * scale for k < lens[i] — one fp32 product, rounded once, then for fp16 one
+ * conversion to nearest-even (overflow gives inf, subnormals are kept) — and +0 from there to offsets[i + 1],
+ * whatever the scale (the reference's `out[id] = 0.0f`).  scale_dev != NULL: the factor is a device word read
+ * once at the top of the kernel (scale is then not used) — result + 2 of mhte_global_l2_reduce; a captured
+ * graph replays with whatever the word holds then.  One launch per call, none for n == 0 or a total of 0; no
+ * entry point waits for the device, reads a device value or allocates after the first call.  Up to 128
+ * non-empty tensors travel in the kernel arguments; more are uploaded per call (such a call cannot be
+ * captured into a graph).  Sources that are 16-byte aligned are read with 16-byte loads, others with 4-byte
+ * loads: the same bits.
+ * InvalidArgument, checked on the host before any device call, the entry point's name in the message: a
+ * null argument, n < 0, a negative length, a null pointer for a non-empty tensor, an align_elems that is
+ * not a power of two in [4, 1024], a wire other than 0 or 1, out_elems != offsets[n], an out that is not
+ * 16-byte aligned, 2^31 or more chunks of 4096 elements.
+ *   mhte_aligned_flat_offsets   the layout alone: host only, no device call
+ *   mhte_aligned_flat_concat    MonolithAlignedFlatConcat (+ the fp16 compression of the allreduce)
+ *   mhte_aligned_flat_decode    out[k] = float(flat[k]) * post_scale over total_elems elements: the way back
+ *                               from the wire format and the division by the number of ranks (the
+ *                               reference's op=Average); fp32 may be decoded in place (out == flat).
+ *                               MonolithAlignedFlatSplit itself copies nothing: its outputs are views at
+ *                               offsets[i] (monolith_amd/distribution_ops.py aligned_flat_split) */
+mhte_status mhte_aligned_flat_offsets(const int64_t* lens, int32_t n, int32_t align_elems, int64_t* offsets);
+mhte_status mhte_aligned_flat_concat(const float* const* inputs, const int64_t* lens, int32_t n, int32_t align_elems,
+                                     float scale, const float* scale_dev, int32_t wire, void* out, int64_t out_elems,
+                                     void* stream);
+mhte_status mhte_aligned_flat_decode(const void* flat, int32_t wire, int64_t total_elems, float post_scale, float* out,
+                                     void* stream);
+
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
  * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op

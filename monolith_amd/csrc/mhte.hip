@@ -39,6 +39,7 @@
 #include "mhte_pool_kernels.h"
 #include "mhte_pool_split_kernels.h"
 #include "mhte_clip_kernels.h"
+#include "mhte_flat_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
@@ -2474,6 +2475,7 @@ struct AuxWs {
   DevBuf<uint32_t> inverse, seg_off, seg_pos, nu;
   DevBuf<float> clip_partials;   // clip by global norm (mhte_clip_host.h): the 1024 partial sums of squares
   DevBuf<char> clip_table;       // ... and the tensor table of a call with more than 128 tensors
+  DevBuf<char> flat_table;       // aligned flat concat (mhte_flat_host.h): the same for its calls
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;
@@ -2708,6 +2710,7 @@ static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* o
 }
 }  // namespace mhte
 #include "mhte_clip_host.h"
+#include "mhte_flat_host.h"
 }  // extern "C++"
 
 mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
@@ -2843,6 +2846,57 @@ mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* out
     ClipTable T;
     clip_build(T, op, inputs, outputs, lens, n, false);
     clip_scale_launch(T, kClipScaleWord, 1.f, scale_dev, 0.f, S(stream));
+  });
+}
+
+// ---- aligned flat concat / split (csrc/mhte_flat_kernels.h, mhte_flat_host.h) -------------------------
+mhte_status mhte_aligned_flat_offsets(const int64_t* lens, int32_t n, int32_t align_elems, int64_t* offsets) {
+  return guard([&] {
+    const char* op = "aligned_flat_offsets";
+    if (!lens) clip_bad(op, "null argument: lens");
+    if (!offsets) clip_bad(op, "null argument: offsets");
+    if (n < 0) clip_bad(op, "n must be >= 0, got " + std::to_string(n));
+    for (int32_t i = 0; i < n; ++i)
+      if (lens[i] < 0) clip_bad(op, "tensor " + std::to_string(i) + " has the negative length " + std::to_string(lens[i]));
+    flat_check_align(op, align_elems);
+    (void)flat_offsets(op, lens, n, align_elems, offsets);
+  });
+}
+
+mhte_status mhte_aligned_flat_concat(const float* const* inputs, const int64_t* lens, int32_t n, int32_t align_elems,
+                                     float scale, const float* scale_dev, int32_t wire, void* out, int64_t out_elems,
+                                     void* stream) {
+  return guard([&] {
+    const char* op = "aligned_flat_concat";
+    if (!inputs) clip_bad(op, "null argument: inputs");
+    if (!lens) clip_bad(op, "null argument: lens");
+    clip_check(op, inputs, "inputs", nullptr, lens, n, false, 0.f);
+    flat_check_align(op, align_elems);
+    if (wire != 0 && wire != 1) clip_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
+    const int64_t total = flat_offsets(op, lens, n, align_elems, nullptr);
+    if (out_elems != total)
+      clip_bad(op, "out_elems must be the aligned total " + std::to_string(total) + ", got " + std::to_string(out_elems));
+    if (total && !out) clip_bad(op, "null argument: out");
+    if (!aligned16(out)) clip_bad(op, "out must be 16-byte aligned");
+    FlatTable T;
+    flat_build(T, op, inputs, lens, n, align_elems);
+    clip_need_device();
+    flat_concat_launch(T, scale, scale_dev, wire, out, S(stream));
+  });
+}
+
+mhte_status mhte_aligned_flat_decode(const void* flat, int32_t wire, int64_t total_elems, float post_scale, float* out,
+                                     void* stream) {
+  return guard([&] {
+    const char* op = "aligned_flat_decode";
+    if (total_elems < 0) clip_bad(op, "total_elems must be >= 0, got " + std::to_string(total_elems));
+    if (wire != 0 && wire != 1) clip_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
+    if (total_elems && !flat) clip_bad(op, "null argument: flat");
+    if (total_elems && !out) clip_bad(op, "null argument: out");
+    if (wire == 1 && total_elems && static_cast<const void*>(out) == flat)
+      clip_bad(op, "an fp16 flat buffer is not decoded in place");
+    clip_need_device();
+    flat_decode_launch(flat, wire, total_elems, post_scale, out, S(stream));
   });
 }
 

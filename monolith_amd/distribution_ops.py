@@ -610,3 +610,95 @@ def lookup_gradient(id_indices: torch.Tensor, id_values: torch.Tensor,
       _lib.vp(out),
       _lib.C.c_void_p(torch.cuda.current_stream().cuda_stream)))
   return out_ids, out
+
+
+# ---- aligned flat concat / split: the allreduce side of the deferred clip -------------------------------
+_WIRE = {torch.float32: 0, torch.float16: 1}
+
+
+def _numel_of(x) -> int:
+  if isinstance(x, torch.Tensor):
+    return x.numel()
+  n = 1
+  for d in x:   # a shape
+    n *= int(d)
+  return n
+
+
+def aligned_flat_offsets(numels: List[int], align: int = 16) -> List[int]:
+  """FusedAlignedOutputAllocator's rule (runtime/ops/alloc_utils.h:50-95): ``n + 1`` offsets in elements,
+  tensor i starts at the sum of ``round_up(numels[j], align)`` over j < i, the last entry is the aligned
+  total.  ``align`` is in elements, a power of two in [4, 1024]; the default of 16 floats is the 64-byte
+  EIGEN_MAX_ALIGN_BYTES / sizeof(float) of TF's builds (the reference's value depends on its build)."""
+  n = len(numels)
+  lens = (C.c_int64 * max(n, 1))(*[int(v) for v in numels])
+  offs = (C.c_int64 * (n + 1))()
+  check(_lib.lib().mhte_aligned_flat_offsets(lens, n, int(align), offs))
+  return list(offs)
+
+
+def aligned_flat_concat(tensors: List[torch.Tensor], scale=1.0, wire_dtype: torch.dtype = torch.float32,
+                        align: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """MonolithAlignedFlatConcat (runtime/ops/aligned_concat_split.cu.cc:32-57, :63-109): the flattened tensors
+  times ``scale`` in one flat buffer, every tensor's start aligned to ``align`` elements
+  (``aligned_flat_offsets``), the padding +0 — one launch.  ``scale``: a Python float, or a 0-d float32
+  device tensor (``clip_ops.global_norm_and_scale``) that is read on the device.  ``wire_dtype``
+  torch.float16 rounds every product to nearest-even on the way out (the FP16Compressor of the reference's
+  allreduce; values beyond 65504 become inf).  ``out``: a 1-d contiguous buffer of ``wire_dtype`` with the
+  aligned total's elements to fill instead of a new one."""
+  if not isinstance(tensors, list):
+    raise TypeError("tensors should be a list")
+  if wire_dtype not in _WIRE:
+    raise TypeError("aligned_flat_concat: wire_dtype must be torch.float32 or torch.float16")
+  ins = []
+  for t in tensors:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+      raise TypeError("aligned_flat_concat: the tensors must be float32 tensors on the GPU")
+    ins.append(t if t.is_contiguous() else t.contiguous())
+  if not ins and out is None:
+    raise ValueError("aligned_flat_concat: an empty list has no device to keep the result on")
+  n = len(ins)
+  total = aligned_flat_offsets([t.numel() for t in ins], align)[-1]
+  if out is None:
+    out = torch.empty(total, dtype=wire_dtype, device=ins[0].device)
+  elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == wire_dtype and out.dim() == 1 and
+            out.is_contiguous() and out.numel() == total):
+    raise ValueError("aligned_flat_concat: out must be a contiguous 1-d %s tensor on the GPU with %d elements" %
+                     (wire_dtype, total))
+  pin = (C.c_void_p * max(n, 1))(*[C.c_void_p(t.data_ptr()) for t in ins])
+  lens = (C.c_int64 * max(n, 1))(*[t.numel() for t in ins])
+  if isinstance(scale, torch.Tensor):
+    if not (scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1):
+      raise TypeError("aligned_flat_concat: scale must be a float or a 0-d float32 tensor on the GPU")
+    host, dev = 1.0, vp(scale)
+  else:
+    host, dev = float(scale), None
+  check(_lib.lib().mhte_aligned_flat_concat(pin, lens, n, int(align), host, dev, _WIRE[wire_dtype], vp(out),
+                                            total, _stream()))
+  return out
+
+
+def aligned_flat_split(like, flat: torch.Tensor, post_scale: Optional[float] = None,
+                       align: int = 16) -> List[torch.Tensor]:
+  """MonolithAlignedFlatSplit (runtime/ops/aligned_concat_split.cu.cc:111-128): the tensors of a flat buffer
+  with the shapes of ``like`` (tensors, read for their shapes only, or shapes).  A float32 ``flat`` with
+  ``post_scale=None`` launches nothing: the results are VIEWS of ``flat`` at ``aligned_flat_offsets``,
+  zero-copy as the reference's ``get_slice`` is.  Otherwise one launch computes
+  ``float(flat) * post_scale`` first — a float32 ``flat`` in place, a float16 one into a new float32
+  buffer (``post_scale=None`` is then 1) — and the results are views of that."""
+  if not isinstance(like, (list, tuple)):
+    raise TypeError("like should be a list")
+  if not (isinstance(flat, torch.Tensor) and flat.dtype in _WIRE and flat.dim() == 1 and flat.is_contiguous()):
+    raise TypeError("aligned_flat_split: flat must be a contiguous 1-d float32 or float16 tensor")
+  shapes = [tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(int(d) for d in x) for x in like]
+  offs = aligned_flat_offsets([_numel_of(s) for s in shapes], align)
+  if flat.numel() != offs[-1]:
+    raise ValueError("aligned_flat_split: flat has %d elements, the shapes need %d" % (flat.numel(), offs[-1]))
+  if flat.dtype != torch.float32 or post_scale is not None:
+    if not flat.is_cuda:
+      raise TypeError("aligned_flat_split: decoding needs a flat buffer on the GPU")
+    dst = flat if flat.dtype == torch.float32 else torch.empty(flat.numel(), dtype=torch.float32, device=flat.device)
+    check(_lib.lib().mhte_aligned_flat_decode(vp(flat), _WIRE[flat.dtype], flat.numel(),
+                                              1.0 if post_scale is None else float(post_scale), vp(dst), _stream()))
+    flat = dst
+  return [flat[o:o + _numel_of(s)].view(s) for o, s in zip(offs, shapes)]

@@ -1,0 +1,144 @@
+"""The gradient clip and the dense allreduce of a training step on MI355X — host-side mirror of the part of
+monolith/native_training/feature_utils.py that sits between ``compute_gradients`` and the optimizers:
+``allreduce_cond`` (reference :48-99, fusion ``'one'``) and the clip / allreduce order of
+``apply_gradients_with_var_optimizer`` (reference :209-270).
+
+In synchronous GPU training the reference does not clip the dense gradients where it computes their norm: it
+keeps ``scale = min(clip_norm / norm, 1)`` as a tensor (``cond_defer_clip``, :251-260) and hands it to
+``MonolithAlignedFlatConcat``, which multiplies while it packs all dense gradients into one aligned flat
+buffer; one allreduce (average) runs over that buffer, optionally cast to fp16 (``enable_allreduce_fp16``),
+and ``MonolithAlignedFlatSplit`` cuts the result back into the gradients' shapes without a copy.  The same
+scale goes to the sparse side (``fused_gather_embeddings_by_input_gradient(scale=...)``,
+``clip_ops.scale_tensors``).  Here the norm, the scale, the concat and the way back are device work only
+(``clip_ops``, ``distribution_ops.aligned_flat_concat`` / ``aligned_flat_split``): no function of this module
+waits for the GPU or reads a device value.
+
+The collective itself is the caller's: ``torch.distributed.all_reduce`` by default, any callable otherwise.
+
+fp16 on the wire: every product is rounded to fp16 before the ranks' buffers are added, and the SUM is formed
+in fp16 by the collective — it overflows to inf beyond 65504 although the average would fit, and gradients
+below 6e-8 vanish.  That is the reference's behaviour too (its FP16Compressor casts before the allreduce);
+the clip bounds the norm of one rank's gradients, not the sum over the ranks.
+
+Not restated: the ``'grouped'`` fusion and the un-fused allreduce of the reference, ``ClipByNorm`` and
+``ClipByValue``, the norm warm-up, and the summaries.
+"""
+import enum
+from typing import Callable, List, Optional, Tuple
+
+import torch
+
+from monolith_amd import clip_ops
+from monolith_amd import distribution_ops
+
+
+class GradClipType(enum.Enum):
+  """feature_utils.GradClipType (reference :102-107)."""
+  ClipByNorm = 1
+  ClipByGlobalNorm = 2
+  ClipByValue = 3
+  ClipByDenseAndSparse = 4
+  NoClip = 5
+
+
+def _world_of(group) -> int:
+  import torch.distributed as dist  # pylint: disable=import-outside-toplevel
+  if dist.is_available() and dist.is_initialized():
+    return dist.get_world_size(group)
+  return 1
+
+
+def allreduce_cond(grads: List[Optional[torch.Tensor]], scale=1, fp16: bool = False, group=None,
+                   allreduce: Optional[Callable[[torch.Tensor], Optional[torch.Tensor]]] = None,
+                   world: Optional[int] = None, align: int = 16) -> List[Optional[torch.Tensor]]:
+  """feature_utils.allreduce_cond with fusion ``'one'`` (reference :48-81): the average over the ranks of
+  ``grad * scale`` for every gradient of the list.  ``None`` entries keep their places (``map_to_output``),
+  and a list of ``None`` only is returned as it is.
+
+  concat (``scale`` applied, fp16 wire when ``fp16``) -> ``allreduce(flat)`` -> split with
+  ``post_scale = 1 / world``.  ``scale``: a Python number or a 0-d float32 device tensor.  ``allreduce``
+  takes the flat buffer and sums it over the ranks, in place or into the buffer it returns; the default is
+  ``torch.distributed.all_reduce(flat, SUM, group)``.  ``world`` defaults to the group's size; with
+  ``torch.distributed`` not initialised it is 1 and there is no collective.  With one rank and an fp32 wire
+  the results are views of the concat's buffer and nothing else is launched (a factor of exactly 1)."""
+  wo_none = [g for g in grads if g is not None]
+  if not wo_none:
+    return grads
+  if world is None:
+    world = _world_of(group)
+  world = int(world)
+  if world < 1:
+    raise ValueError("allreduce_cond: world must be >= 1, got %d" % world)
+  flat = distribution_ops.aligned_flat_concat(wo_none, scale=scale,
+                                              wire_dtype=torch.float16 if fp16 else torch.float32, align=align)
+  if allreduce is not None:
+    reduced = allreduce(flat)
+    flat = flat if reduced is None else reduced
+  elif world > 1:
+    import torch.distributed as dist  # pylint: disable=import-outside-toplevel
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+  post_scale = None if world == 1 else 1.0 / world
+  reduced = distribution_ops.aligned_flat_split(wo_none, flat, post_scale=post_scale, align=align)
+  it = iter(reduced)
+  return [None if g is None else next(it) for g in grads]
+
+
+def _device_of(tensors) -> torch.device:
+  for t in tensors:
+    if t is not None:
+      return t.device
+  return torch.device("cuda")
+
+
+def clip_and_allreduce(dense_grads: List[Optional[torch.Tensor]], sparse_grads: List[Optional[torch.Tensor]],
+                       clip_type: GradClipType = GradClipType.ClipByGlobalNorm,
+                       clip_norm: Optional[float] = None, sparse_clip_norm: Optional[float] = None,
+                       use_allreduce: bool = False, fp16: bool = False, group=None, allreduce=None,
+                       world: Optional[int] = None,
+                       align: int = 16) -> Tuple[List[Optional[torch.Tensor]], torch.Tensor]:
+  """The clip and the dense allreduce of apply_gradients_with_var_optimizer (reference :209-270, :298-303)
+  -> ``(dense_grads_out, sparse_scale)``.
+
+  * ``ClipByGlobalNorm`` with a ``clip_norm``: ONE norm over dense + sparse gradients (:213-216);
+    ``sparse_clip_norm`` defaults to ``clip_norm``.
+  * ``ClipByDenseAndSparse``: one norm over the dense gradients, and one over the sparse ones when there is a
+    ``sparse_clip_norm`` (:231-234).
+  * ``NoClip`` (or no ``clip_norm``): both scales are 1.
+  Norm and ``scale = norm > clip ? clip / norm : 1`` come from ``clip_ops.global_norm_and_scale`` and stay on
+  the device.  With ``use_allreduce`` the dense clip is deferred (``cond_defer_clip``, :251-260): the scale is
+  multiplied in by the concat of ``allreduce_cond``.  Without it the dense gradients are clipped by
+  ``clip_ops.clip_by_global_norm`` with that norm and nothing is reduced.  The sparse side is always
+  deferred: ``sparse_scale`` is a 0-d float32 device tensor for
+  ``distribution_ops.fused_gather_embeddings_by_input_gradient(scale=...)`` and ``clip_ops.scale_tensors``.
+  ``None`` gradients keep their places and take no part in a norm."""
+  if not isinstance(clip_type, GradClipType):
+    raise TypeError("clip_type must be a GradClipType")
+  if clip_type in (GradClipType.ClipByNorm, GradClipType.ClipByValue):
+    raise NotImplementedError("clip_and_allreduce: %s is not restated here" % clip_type.name)
+  dense = [g for g in dense_grads if g is not None]
+  sparse = [g for g in sparse_grads if g is not None]
+  dense_norm = dense_scale = sparse_scale = None
+  if clip_type == GradClipType.ClipByGlobalNorm and clip_norm is not None and dense + sparse:
+    dense_norm, dense_scale = clip_ops.global_norm_and_scale(dense + sparse, clip_norm)
+    sparse_clip_norm = sparse_clip_norm or clip_norm
+    if float(sparse_clip_norm) == float(clip_norm):
+      sparse_scale = dense_scale
+    else:   # the same norm against another bound: computed again, on the device
+      sparse_scale = clip_ops.global_norm_and_scale(dense + sparse, sparse_clip_norm)[1]
+  elif clip_type == GradClipType.ClipByDenseAndSparse:
+    if clip_norm is not None and dense:
+      dense_norm, dense_scale = clip_ops.global_norm_and_scale(dense, clip_norm)
+    if sparse_clip_norm is not None and sparse:
+      sparse_scale = clip_ops.global_norm_and_scale(sparse, sparse_clip_norm)[1]
+  if sparse_scale is None:
+    sparse_scale = torch.ones((), dtype=torch.float32, device=_device_of(list(dense_grads) + list(sparse_grads)))
+  if use_allreduce:
+    out = allreduce_cond(dense_grads, scale=1 if dense_scale is None else dense_scale, fp16=fp16, group=group,
+                         allreduce=allreduce, world=world, align=align)
+  elif dense_norm is not None and dense:
+    clipped, _ = clip_ops.clip_by_global_norm(dense, clip_norm, use_norm=dense_norm)
+    it = iter(clipped)
+    out = [None if g is None else next(it) for g in dense_grads]
+  else:
+    out = list(dense_grads)
+  return out, sparse_scale
