@@ -439,6 +439,62 @@ mhte_status mhte_aligned_flat_concat(const float* const* inputs, const int64_t* 
 mhte_status mhte_aligned_flat_decode(const void* flat, int32_t wire, int64_t total_elems, float post_scale, float* out,
                                      void* stream);
 
+/* ---- dense optimizers (csrc/mhte_dense_opt_core.h, mhte_dense_opt_kernels.h) --------------------------
+ * ResourceApplyAdamom (the reference's is CPU only) and ResourceApplyRmsprop V1 / V2
+ * (NT/optimizers/{adamom,rmsprop}.py, NT/optimizers/cc/training_ops.cc, NT/optimizers/cc/kernels/
+ * training_ops{.h,.cc,_gpu.cu.cc}; the expression trees of kernels/training_ops.cc:34-121), applied to ALL
+ * variables in ONE launch: what consumes the gradients of the deferred clip and the aligned flat allreduce.
+ *   vars          HOST array of n device pointers (fp32, updated in place); lens HOST [n], floats per variable
+ *                 (0 is legal: the variable occupies nothing and its pointer is not looked at)
+ *   m, v, c       [dev f32, slot_elems] the FLAT slots, 16-byte aligned, in the layout of
+ *                 mhte_aligned_flat_offsets(lens, align_elems): element k of variable i lives at offsets[i] + k,
+ *                 slot_elems == offsets[n]; the padding between variables is never read or written
+ *   the gradient  exactly one of
+ *                   grads       HOST array of n device pointers (fp32; wire must be 0).  A NULL entry: the
+ *                               variable takes no part in this call — its var and all its slot elements,
+ *                               Adamom's c included, keep their bits (TensorFlow skips None gradients too);
+ *                   grads_flat  [dev, slot_elems] ONE flat buffer in the same aligned layout, fp32 (wire 0) or
+ *                               fp16 (wire 1), 16-byte aligned: where the allreduce left the gradients
+ *   grad_scale / grad_scale_dev, lr / lr_dev   each a kernel argument or, when the pointer is not NULL, a
+ *                 device word read once at the top of the kernel (the argument is then not used): result + 2
+ *                 of mhte_global_l2_reduce, a learning-rate schedule that stays on the device.  A captured
+ *                 graph replays with whatever the words hold then.
+ * Per element, everything fp32, every operation rounded on its own (no FMA), sqrt and / correctly rounded,
+ * rsqrt(x) := 1 / sqrt(x); g0 the gradient element (an fp16 one converted exactly):
+ *   grad = g0 * grad_scale                 (always one rounded product, also for a scale of 1)
+ *   g    = (weight_decay * var) + grad
+ *   Adamom:   if update_slots:  m = (mom_decay * m) + ((1 - mom_decay) * g);  v = (ada_decay * v) + (g * g);
+ *                               c = (ada_decay * c) + 1
+ *             v1: var = var - ((m * lr) * rsqrt((v / c) + epsilon))
+ *             v2: var = var - ((m * lr) / (sqrt(v / c) + epsilon))
+ *             update_slots == 0 still moves var (fresh slots give 0 / 0: NaN, as IEEE has it)
+ *   RMSprop:  v1: v = v + (((g * g) - v) * (1 - beta2));  m = (beta1 * m) + ((g * lr) * rsqrt(v + epsilon))
+ *             v2: v = (beta2 * v) + (g * g);              m = (beta1 * m) + ((g * lr) / (sqrt(v) + epsilon))
+ *             var = var - m;  update_slots == 0 changes nothing at all and launches nothing
+ * (not the sparse per-row RMSprop of the tables, RT/hash_table/optimizer/rmsprop_optimizer.cc).
+ * One launch per call, none for n == 0 or when no element takes part; no entry point waits for the device,
+ * reads a device value or allocates after the first call.  Up to MHTE_DENSE_OPT_INLINE variables that take
+ * part travel in the kernel arguments; more are uploaded per call (such a call cannot be captured into a
+ * graph).  16-byte accesses where a pointer is 16-byte aligned, else 4-byte ones (same bits); packed 8-byte
+ * loads for an fp16 gradient.
+ * InvalidArgument, checked on the host before any device call, the entry point's name in the message: a
+ * null required argument, n < 0, a negative length, a null vars[i] for a non-empty variable, both or neither
+ * of grads / grads_flat, a wire other than 0 or 1, wire 1 with the list, an align_elems that is not a power
+ * of two in [4, 1024], slot_elems != offsets[n], a slot or flat buffer that is not 16-byte aligned, 2^31 or
+ * more chunks of 4096 elements, update_slots or use_v2 other than 0 or 1. */
+#define MHTE_DENSE_OPT_INLINE 96
+mhte_status mhte_dense_apply_adamom(float* const* vars, const int64_t* lens, int32_t n, int32_t align_elems, float* m,
+                                    float* v, float* c, int64_t slot_elems, const float* const* grads,
+                                    const void* grads_flat, int32_t wire, float grad_scale,
+                                    const float* grad_scale_dev, float lr, const float* lr_dev, float ada_decay,
+                                    float mom_decay, float epsilon, float weight_decay, int32_t update_slots,
+                                    int32_t use_v2, void* stream);
+mhte_status mhte_dense_apply_rmsprop(float* const* vars, const int64_t* lens, int32_t n, int32_t align_elems, float* m,
+                                     float* v, int64_t slot_elems, const float* const* grads, const void* grads_flat,
+                                     int32_t wire, float grad_scale, const float* grad_scale_dev, float lr,
+                                     const float* lr_dev, float beta1, float beta2, float epsilon, float weight_decay,
+                                     int32_t update_slots, int32_t use_v2, void* stream);
+
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
  * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op

@@ -88,6 +88,8 @@ class TableStats(C.Structure):
 # ---- the binding, read from the header: it is the description of the ABI ----------------------
 _HEADER_TEXT = open(_HEADER).read()
 ABI_VERSION = int(re.search(r"^#define\s+MHTE_ABI_VERSION\s+(\d+)", _HEADER_TEXT, re.M).group(1))
+# variables of a dense-optimizer call that travel in the kernel arguments (more: an upload per call)
+DENSE_OPT_INLINE = int(re.search(r"^#define\s+MHTE_DENSE_OPT_INLINE\s+(\d+)", _HEADER_TEXT, re.M).group(1))
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
             "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double,

@@ -40,6 +40,7 @@
 #include "mhte_pool_split_kernels.h"
 #include "mhte_clip_kernels.h"
 #include "mhte_flat_kernels.h"
+#include "mhte_dense_opt_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
@@ -2476,6 +2477,7 @@ struct AuxWs {
   DevBuf<float> clip_partials;   // clip by global norm (mhte_clip_host.h): the 1024 partial sums of squares
   DevBuf<char> clip_table;       // ... and the tensor table of a call with more than 128 tensors
   DevBuf<char> flat_table;       // aligned flat concat (mhte_flat_host.h): the same for its calls
+  DevBuf<char> dense_opt_table;  // dense optimizers (mhte_dense_opt_host.h): the same, beyond 96 variables
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;
@@ -2711,6 +2713,7 @@ static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* o
 }  // namespace mhte
 #include "mhte_clip_host.h"
 #include "mhte_flat_host.h"
+#include "mhte_dense_opt_host.h"
 }  // extern "C++"
 
 mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
@@ -2897,6 +2900,41 @@ mhte_status mhte_aligned_flat_decode(const void* flat, int32_t wire, int64_t tot
       clip_bad(op, "an fp16 flat buffer is not decoded in place");
     clip_need_device();
     flat_decode_launch(flat, wire, total_elems, post_scale, out, S(stream));
+  });
+}
+
+// ---- dense optimizers (csrc/mhte_dense_opt_core.h, mhte_dense_opt_kernels.h, mhte_dense_opt_host.h) ---
+mhte_status mhte_dense_apply_adamom(float* const* vars, const int64_t* lens, int32_t n, int32_t align_elems, float* m,
+                                    float* v, float* c, int64_t slot_elems, const float* const* grads,
+                                    const void* grads_flat, int32_t wire, float grad_scale,
+                                    const float* grad_scale_dev, float lr, const float* lr_dev, float ada_decay,
+                                    float mom_decay, float epsilon, float weight_decay, int32_t update_slots,
+                                    int32_t use_v2, void* stream) {
+  return guard([&] {
+    const DenseOptCall q{vars, lens, n, align_elems, m, v, c, slot_elems, grads, grads_flat, wire,
+                         grad_scale_dev, lr_dev, update_slots, use_v2};
+    DenseOptTable T;
+    dense_opt_check("dense_apply_adamom", q, /*c_needed=*/true, T);
+    clip_need_device();
+    const DenseOptHyper h{grad_scale, lr, ada_decay, mom_decay, epsilon, weight_decay};
+    dense_opt_launch<kDenseAdamom>(T, q, h, S(stream));
+  });
+}
+
+mhte_status mhte_dense_apply_rmsprop(float* const* vars, const int64_t* lens, int32_t n, int32_t align_elems, float* m,
+                                     float* v, int64_t slot_elems, const float* const* grads, const void* grads_flat,
+                                     int32_t wire, float grad_scale, const float* grad_scale_dev, float lr,
+                                     const float* lr_dev, float beta1, float beta2, float epsilon, float weight_decay,
+                                     int32_t update_slots, int32_t use_v2, void* stream) {
+  return guard([&] {
+    const DenseOptCall q{vars, lens, n, align_elems, m, v, nullptr, slot_elems, grads, grads_flat, wire,
+                         grad_scale_dev, lr_dev, update_slots, use_v2};
+    DenseOptTable T;
+    dense_opt_check("dense_apply_rmsprop", q, /*c_needed=*/false, T);
+    clip_need_device();
+    if (!update_slots) return;   // (training_ops.cc:45, :66: without update_slots the op changes nothing)
+    const DenseOptHyper h{grad_scale, lr, beta1, beta2, epsilon, weight_decay};
+    dense_opt_launch<kDenseRmsprop>(T, q, h, S(stream));
   });
 }
 

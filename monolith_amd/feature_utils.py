@@ -15,6 +15,10 @@ waits for the GPU or reads a device value.
 
 The collective itself is the caller's: ``torch.distributed.all_reduce`` by default, any callable otherwise.
 
+``clip_allreduce_and_apply`` goes one step further, to the reference's ``var_opt.apply_gradients``: the dense
+optimizers of ``monolith_amd.optimizers`` read the flat buffer where the allreduce left it (or the gradient
+list with the deferred scale), so neither a clipped nor a decoded copy of the gradients is written.
+
 fp16 on the wire: every product is rounded to fp16 before the ranks' buffers are added, and the SUM is formed
 in fp16 by the collective — it overflows to inf beyond 65504 although the average would fit, and gradients
 below 6e-8 vanish.  That is the reference's behaviour too (its FP16Compressor casts before the allreduce);
@@ -90,27 +94,9 @@ def _device_of(tensors) -> torch.device:
   return torch.device("cuda")
 
 
-def clip_and_allreduce(dense_grads: List[Optional[torch.Tensor]], sparse_grads: List[Optional[torch.Tensor]],
-                       clip_type: GradClipType = GradClipType.ClipByGlobalNorm,
-                       clip_norm: Optional[float] = None, sparse_clip_norm: Optional[float] = None,
-                       use_allreduce: bool = False, fp16: bool = False, group=None, allreduce=None,
-                       world: Optional[int] = None,
-                       align: int = 16) -> Tuple[List[Optional[torch.Tensor]], torch.Tensor]:
-  """The clip and the dense allreduce of apply_gradients_with_var_optimizer (reference :209-270, :298-303)
-  -> ``(dense_grads_out, sparse_scale)``.
-
-  * ``ClipByGlobalNorm`` with a ``clip_norm``: ONE norm over dense + sparse gradients (:213-216);
-    ``sparse_clip_norm`` defaults to ``clip_norm``.
-  * ``ClipByDenseAndSparse``: one norm over the dense gradients, and one over the sparse ones when there is a
-    ``sparse_clip_norm`` (:231-234).
-  * ``NoClip`` (or no ``clip_norm``): both scales are 1.
-  Norm and ``scale = norm > clip ? clip / norm : 1`` come from ``clip_ops.global_norm_and_scale`` and stay on
-  the device.  With ``use_allreduce`` the dense clip is deferred (``cond_defer_clip``, :251-260): the scale is
-  multiplied in by the concat of ``allreduce_cond``.  Without it the dense gradients are clipped by
-  ``clip_ops.clip_by_global_norm`` with that norm and nothing is reduced.  The sparse side is always
-  deferred: ``sparse_scale`` is a 0-d float32 device tensor for
-  ``distribution_ops.fused_gather_embeddings_by_input_gradient(scale=...)`` and ``clip_ops.scale_tensors``.
-  ``None`` gradients keep their places and take no part in a norm."""
+def _norms_and_scales(dense_grads, sparse_grads, clip_type, clip_norm, sparse_clip_norm):
+  """The norms of apply_gradients_with_var_optimizer (reference :211-234) -> ``(dense_norm, dense_scale,
+  sparse_scale)``: 0-d device tensors; the dense pair is ``None`` where nothing clips the dense side."""
   if not isinstance(clip_type, GradClipType):
     raise TypeError("clip_type must be a GradClipType")
   if clip_type in (GradClipType.ClipByNorm, GradClipType.ClipByValue):
@@ -132,6 +118,33 @@ def clip_and_allreduce(dense_grads: List[Optional[torch.Tensor]], sparse_grads: 
       sparse_scale = clip_ops.global_norm_and_scale(sparse, sparse_clip_norm)[1]
   if sparse_scale is None:
     sparse_scale = torch.ones((), dtype=torch.float32, device=_device_of(list(dense_grads) + list(sparse_grads)))
+  return dense_norm, dense_scale, sparse_scale
+
+
+def clip_and_allreduce(dense_grads: List[Optional[torch.Tensor]], sparse_grads: List[Optional[torch.Tensor]],
+                       clip_type: GradClipType = GradClipType.ClipByGlobalNorm,
+                       clip_norm: Optional[float] = None, sparse_clip_norm: Optional[float] = None,
+                       use_allreduce: bool = False, fp16: bool = False, group=None, allreduce=None,
+                       world: Optional[int] = None,
+                       align: int = 16) -> Tuple[List[Optional[torch.Tensor]], torch.Tensor]:
+  """The clip and the dense allreduce of apply_gradients_with_var_optimizer (reference :209-270, :298-303)
+  -> ``(dense_grads_out, sparse_scale)``.
+
+  * ``ClipByGlobalNorm`` with a ``clip_norm``: ONE norm over dense + sparse gradients (:213-216);
+    ``sparse_clip_norm`` defaults to ``clip_norm``.
+  * ``ClipByDenseAndSparse``: one norm over the dense gradients, and one over the sparse ones when there is a
+    ``sparse_clip_norm`` (:231-234).
+  * ``NoClip`` (or no ``clip_norm``): both scales are 1.
+  Norm and ``scale = norm > clip ? clip / norm : 1`` come from ``clip_ops.global_norm_and_scale`` and stay on
+  the device.  With ``use_allreduce`` the dense clip is deferred (``cond_defer_clip``, :251-260): the scale is
+  multiplied in by the concat of ``allreduce_cond``.  Without it the dense gradients are clipped by
+  ``clip_ops.clip_by_global_norm`` with that norm and nothing is reduced.  The sparse side is always
+  deferred: ``sparse_scale`` is a 0-d float32 device tensor for
+  ``distribution_ops.fused_gather_embeddings_by_input_gradient(scale=...)`` and ``clip_ops.scale_tensors``.
+  ``None`` gradients keep their places and take no part in a norm."""
+  dense_norm, dense_scale, sparse_scale = _norms_and_scales(dense_grads, sparse_grads, clip_type, clip_norm,
+                                                            sparse_clip_norm)
+  dense = [g for g in dense_grads if g is not None]
   if use_allreduce:
     out = allreduce_cond(dense_grads, scale=1 if dense_scale is None else dense_scale, fp16=fp16, group=group,
                          allreduce=allreduce, world=world, align=align)
@@ -142,3 +155,52 @@ def clip_and_allreduce(dense_grads: List[Optional[torch.Tensor]], sparse_grads: 
   else:
     out = list(dense_grads)
   return out, sparse_scale
+
+
+def clip_allreduce_and_apply(optimizer, grads_and_vars, sparse_grads: List[Optional[torch.Tensor]],
+                             clip_type: GradClipType = GradClipType.ClipByGlobalNorm,
+                             clip_norm: Optional[float] = None, sparse_clip_norm: Optional[float] = None,
+                             use_allreduce: bool = False, fp16: bool = False, group=None, allreduce=None,
+                             world: Optional[int] = None, update_slots: bool = True) -> torch.Tensor:
+  """``clip_and_allreduce`` with the dense apply at its end (reference :209-270 down to
+  ``var_opt.apply_gradients``) -> ``sparse_scale``.  ``optimizer``: an ``optimizers.AdamomOptimizer`` or
+  ``RmspropOptimizer``; ``grads_and_vars``: the dense (gradient, variable) pairs in the optimizer's order.
+
+  Norms and scales as in ``clip_and_allreduce``.  The dense clip is ALWAYS deferred here and no clipped copy
+  of the gradients is written:
+  * with ``use_allreduce``: concat (the scale multiplied in, fp16 wire when ``fp16``, the optimizer's
+    ``align``) -> the collective -> ``optimizer.apply_flat(flat, post_scale=1 / world)``, which reads the
+    gradients where the allreduce left them.  Every variable needs a gradient: the flat buffer has the layout
+    of the optimizer's slots.
+  * without: ``optimizer.apply_gradients(..., grad_scale=dense_scale)``; ``None`` gradients are skipped.
+  Both multiply by ``scale = norm > clip_norm ? clip_norm / norm : 1``, as the reference's synchronous path
+  does (``cond_defer_clip``).  ``clip_and_allreduce`` without ``use_allreduce`` goes through
+  ``clip_by_global_norm``, whose ``t * clip_norm / max(norm, clip_norm)`` rounds differently: the two agree to
+  a few ulp, not bit for bit."""
+  pairs = list(grads_and_vars)
+  dense_grads = [g for g, _ in pairs]
+  _, dense_scale, sparse_scale = _norms_and_scales(dense_grads, sparse_grads, clip_type, clip_norm,
+                                                   sparse_clip_norm)
+  scale = 1.0 if dense_scale is None else dense_scale
+  if not use_allreduce:
+    optimizer.apply_gradients(pairs, grad_scale=scale, update_slots=update_slots)
+    return sparse_scale
+  if any(g is None for g in dense_grads):
+    raise ValueError("clip_allreduce_and_apply: with use_allreduce every variable needs a gradient")
+  if world is None:
+    world = _world_of(group)
+  world = int(world)
+  if world < 1:
+    raise ValueError("clip_allreduce_and_apply: world must be >= 1, got %d" % world)
+  flat = distribution_ops.aligned_flat_concat(dense_grads, scale=scale,
+                                              wire_dtype=torch.float16 if fp16 else torch.float32,
+                                              align=optimizer.align)
+  if allreduce is not None:
+    reduced = allreduce(flat)
+    flat = flat if reduced is None else reduced
+  elif world > 1:
+    import torch.distributed as dist  # pylint: disable=import-outside-toplevel
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+  optimizer.apply_flat(flat, variables=[v for _, v in pairs], post_scale=None if world == 1 else 1.0 / world,
+                       update_slots=update_slots)
+  return sparse_scale
