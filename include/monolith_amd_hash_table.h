@@ -495,6 +495,40 @@ mhte_status mhte_dense_apply_rmsprop(float* const* vars, const int64_t* lens, in
                                      const float* lr_dev, float beta1, float beta2, float epsilon, float weight_decay,
                                      int32_t update_slots, int32_t use_v2, void* stream);
 
+/* ---- FFM feature cross (csrc/mhte_ffm_core.h, mhte_ffm_kernels.h, mhte_ffm_host.h) ----------------------
+ * The ops FFM and FFMGrad (NT/layers/ops/ffm_ops.cc; shapes and checks NT/layers/kernels/ffm_kernels.h:46-157;
+ * loops ffm_kernels.cc:28-103, ffm_kernels.cu.cc:34-168; Python NT/layers/layer_ops.py:24-46), the cross of the
+ * GroupInt / FFM layer (NT/layers/feature_cross.py:69-146).  All operands [dev f32], row-major, dense:
+ *   left [batch, left_cols], right [batch, right_cols];  L = left_cols / dim_size, R = right_cols / dim_size
+ *   (integer division: columns beyond L * dim_size / R * dim_size are never read), D = dim_size
+ *   int_type 0, multiply:  out [batch, L R D],  out[b, (l R + r) D + k] = left[b, l D + k] * right[b, r D + k]
+ *   int_type 1, dot:       out [batch, L R],    out[b, l R + r] = the sum over k = 0 .. D-1 of those products,
+ *                          started from +0 and taken in ascending k
+ *   mhte_ffm_grad:  grad [batch, grad_cols] with grad_cols / D (multiply) resp. grad_cols (dot) == L R features,
+ *                   left_grad [batch, left_cols], right_grad [batch, right_cols] (full widths; +0 beyond L D / R D):
+ *                     left_grad[b, l D + k]  = +0 + g(l,0,k) right[b, 0 D + k] + ... + g(l,R-1,k) right[b, (R-1) D + k]
+ *                     right_grad[b, r D + k] = +0 + g(0,r,k) left[b, 0 D + k]  + ... + g(L-1,r,k) left[b, (L-1) D + k]
+ *                   g(l,r,k) = grad[b, (l R + r) D + k] (multiply), grad[b, l R + r] (dot); sums left to right
+ * Every product and every sum is one fp32 operation rounded on its own (no FMA), no atomics: the same bits on
+ * every run and in every kernel form.  One launch per call (the gradient: one for both outputs), none for an empty
+ * problem (batch == 0, L == 0 or R == 0; the gradient of an empty cross is cleared without a kernel); no entry
+ * point waits for the device, reads a device value or allocates: a call can be captured into a graph.  16-byte
+ * accesses when D % 4 == 0, the pointers are 16-byte aligned and the row widths multiples of 4 floats, else
+ * 4-byte ones; operands staged in LDS when a batch row's share fits (32 KiB forward, 64 KiB gradient), else read
+ * where they lie.
+ * mhte_ffm_launch_counts: the launches of this process by kernel form, n must be 16, index
+ *   8 * (0 forward, 1 gradient) + 4 * (0 multiply, 1 dot) + 2 * (0 16-byte form, 1 4-byte form) + (0 LDS, 1 direct).
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand, a pointer that is not 4-byte aligned, a negative size,
+ * dim_size < 1, an int_type other than 0 / 1, an out_cols that is not L R D resp. L R, gradient features != L R
+ * ("the in/out shape not match", as FFMGradOp says), batch, a row width or L R D of 2^31 or more. */
+mhte_status mhte_ffm(const float* left, int64_t left_cols, const float* right, int64_t right_cols, int64_t batch,
+                     int32_t dim_size, int32_t int_type, float* out, int64_t out_cols, void* stream);
+mhte_status mhte_ffm_grad(const float* grad, int64_t grad_cols, const float* left, int64_t left_cols,
+                          const float* right, int64_t right_cols, int64_t batch, int32_t dim_size, int32_t int_type,
+                          float* left_grad, float* right_grad, void* stream);
+mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n);
+
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
  * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op

@@ -41,6 +41,7 @@
 #include "mhte_clip_kernels.h"
 #include "mhte_flat_kernels.h"
 #include "mhte_dense_opt_kernels.h"
+#include "mhte_ffm_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
@@ -2714,6 +2715,7 @@ static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* o
 #include "mhte_clip_host.h"
 #include "mhte_flat_host.h"
 #include "mhte_dense_opt_host.h"
+#include "mhte_ffm_host.h"
 }  // extern "C++"
 
 mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
@@ -2935,6 +2937,32 @@ mhte_status mhte_dense_apply_rmsprop(float* const* vars, const int64_t* lens, in
     if (!update_slots) return;   // (training_ops.cc:45, :66: without update_slots the op changes nothing)
     const DenseOptHyper h{grad_scale, lr, beta1, beta2, epsilon, weight_decay};
     dense_opt_launch<kDenseRmsprop>(T, q, h, S(stream));
+  });
+}
+
+// ---- FFM feature cross (csrc/mhte_ffm_core.h, mhte_ffm_kernels.h, mhte_ffm_host.h) ---------------------
+mhte_status mhte_ffm(const float* left, int64_t left_cols, const float* right, int64_t right_cols, int64_t batch,
+                     int32_t dim_size, int32_t int_type, float* out, int64_t out_cols, void* stream) {
+  return guard([&] {
+    ffm_forward(left, left_cols, right, right_cols, batch, dim_size, int_type, out, out_cols, stream);
+  });
+}
+
+mhte_status mhte_ffm_grad(const float* grad, int64_t grad_cols, const float* left, int64_t left_cols,
+                          const float* right, int64_t right_cols, int64_t batch, int32_t dim_size, int32_t int_type,
+                          float* left_grad, float* right_grad, void* stream) {
+  return guard([&] {
+    ffm_gradient(grad, grad_cols, left, left_cols, right, right_cols, batch, dim_size, int_type, left_grad,
+                 right_grad, stream);
+  });
+}
+
+mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    if (!out) clip_bad("ffm_launch_counts", "null argument: out");
+    if (n != kFfmCounters)
+      clip_bad("ffm_launch_counts", "n must be " + std::to_string(kFfmCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kFfmCounters; ++i) out[i] = g_ffm_launches[i].load(std::memory_order_relaxed);
   });
 }
 
