@@ -1143,6 +1143,49 @@ mhte_status mhte_dense_mlp_forward(mhte_dense_mlp* m, const float* x, int64_t ba
                                    void* stream);
 mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* dx,
                                     float learning_rate, void* stream);
+/* Gradients out, parameters in: the joint between the tower and an optimizer that lives outside it (the
+ * dense optimizers of this header, an allreduce, a clip over dense and sparse gradients together).
+ * Additive to ABI 19: new symbols only; mhte_dense_mlp_backward computes the same bits as before.
+ * Both take pointer tables: HOST arrays of n_widths - 1 DEVICE pointers (as mhte_ffm's operands are device
+ * pointers and mhte_fused_reduce_and_split's tables host arrays), GEMM layers 0 .. n_widths - 3 first, then
+ * the row-dot layer.  Shapes are mhte_dense_mlp_get_params': weight [widths[l+1]][widths[l]] and bias
+ * [widths[l+1]]; the row-dot layer [1][widths[n_widths - 2]] and [1].  Neither waits for the device, reads
+ * a device value on the host or allocates (the rule of mhte_ffm).
+ *
+ * mhte_dense_mlp_backward_grads: the backward chain of mhte_dense_mlp_backward (the last layer's backward,
+ * per GEMM layer the split-K weight-gradient GEMM, the bias gradient and the GEMM of the gradient below;
+ * dx optional as there) WITHOUT the SGD step: masters, biases and both bf16 copies keep their bits.  The
+ * fp32 gradients are written to the caller's buffers instead, in the order of every sum of the SGD kernels:
+ *   weight_grads[l][i] = ((+0 + slab_0[i]) + slab_1[i]) + ...  ascending over the split-K slabs of THIS
+ *                        batch (fewer than the handle owns when batch < max_batch)
+ *   bias_grads[l][n]   = the bias gradient as computed (a fixed-order tree over the batch)
+ *   row-dot layer      = per element the 256 strided sums over the 64-row blocks' partials, then the 256-wide
+ *                        tree (bias_grads[last][0] likewise)
+ * so that mhte_dense_mlp_backward(lr) from the same state leaves exactly p - lr * g, rounded once per
+ * operation, in every master.  Launches behind the chain: ONE for all layers, the row-dot layer's tree
+ * included (the layers travel as a table in the kernel arguments; a tower of more than 16 GEMM layers takes
+ * one launch per 16 layers — nothing is uploaded).  A destination that is 16-byte aligned takes 16-byte
+ * accesses, any other 4-byte ones of the same elements: the same bits.  Destinations may lie anywhere, also
+ * inside ONE flat buffer at mhte_aligned_flat_offsets (lens: the shapes above in list order): a caller that
+ * does not clip exports straight into the allreduce buffer and skips mhte_aligned_flat_concat; the padding
+ * between the tensors is not written.
+ * mhte_dense_mlp_load_params: every layer's fp32 parameters from the caller's buffers into the masters, both
+ * bf16 copies (W [N][K] and W^T [K][N], round to nearest even as after mhte_dense_mlp_set_params) and the
+ * row-dot layer's vector and bias, in ONE launch (per 16 GEMM layers).  It does not wait: the sources stay
+ * alive and unchanged until the stream has passed the call.  16-byte loads from a 16-byte aligned source,
+ * 4-byte loads otherwise.
+ * Checked on the host before any device call (MHTE_INVALID_ARGUMENT, "<entry point>: ..."):
+ *   "dense_mlp_backward_grads: null argument: <m | dy | weight_grads | bias_grads | weight_grads[l] | ...>"
+ *   "dense_mlp_backward_grads: <dy | dx | weight_grads[l] | bias_grads[l]> must be 4-byte aligned"
+ *   "dense_mlp_load_params: null argument: <m | weights | biases | weights[l] | biases[l]>"
+ *   "dense_mlp_load_params: <weights[l] | biases[l]> must be 4-byte aligned"
+ * and, without a forward on this handle, MHTE_FAILED_PRECONDITION "dense mlp: backward without a forward".
+ * Sizes cannot be checked from a pointer: a short buffer is the caller's error. */
+mhte_status mhte_dense_mlp_backward_grads(mhte_dense_mlp* m, const float* dy, float* dx,
+                                          float* const* weight_grads, float* const* bias_grads,
+                                          void* stream);
+mhte_status mhte_dense_mlp_load_params(mhte_dense_mlp* m, const float* const* weights,
+                                       const float* const* biases, void* stream);
 /* Read-only: GEMM launches of this handle since create, by role and tile shape (tests assert which
  * instantiation a shape reached).  out[2 * role + tile]: role 0 forward, 1 gradient of a hidden
  * layer, 2 gradient of the input (dx), 3 weight gradient; tile 0 = 128 x 128, 1 = 256 x 256. */

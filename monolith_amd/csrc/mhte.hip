@@ -6144,6 +6144,26 @@ mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* d
     m->m.backward(dy, dx, learning_rate, S(stream));
   });
 }
+mhte_status mhte_dense_mlp_backward_grads(mhte_dense_mlp* m, const float* dy, float* dx,
+                                          float* const* weight_grads, float* const* bias_grads, void* stream) {
+  return guard([&] {
+    DenseMlp::check_ptr("dense_mlp_backward_grads", "m", m, true);
+    DenseMlp::check_ptr("dense_mlp_backward_grads", "dy", dy, true);
+    DenseMlp::check_ptr("dense_mlp_backward_grads", "dx", dx, false);
+    m->m.check_grads_call(weight_grads, bias_grads);
+    HIP_OK(hipSetDevice(m->m.device));
+    m->m.backward_grads(dy, dx, weight_grads, bias_grads, S(stream));
+  });
+}
+mhte_status mhte_dense_mlp_load_params(mhte_dense_mlp* m, const float* const* weights,
+                                       const float* const* biases, void* stream) {
+  return guard([&] {
+    DenseMlp::check_ptr("dense_mlp_load_params", "m", m, true);
+    m->m.check_load_call(weights, biases);
+    HIP_OK(hipSetDevice(m->m.device));
+    m->m.load_params(weights, biases, S(stream));
+  });
+}
 mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]) {
   return guard([&] {
     if (!m || !out) throw Error(MHTE_INVALID_ARGUMENT, "dense mlp: null argument");

@@ -159,8 +159,10 @@ struct DenseMlp {
     HIP_OK(hipGetLastError());
   }
 
-  // dy [B] -> SGD step on every layer; dx [B][w0] (fp32) when not null
-  void backward(const float* dy, float* dx, float lr, hipStream_t st) {
+  // The backward chain up to the gradients, shared by backward (SGD inside) and backward_grads (gradients out):
+  // dy [B] -> per GEMM layer the split-K slabs of dW (split_now of them) and db, part_last of the row-dot
+  // layer; dx [B][w0] (fp32) when not null.  Changes no parameter.
+  void backward_chain(const float* dy, float* dx, hipStream_t st) {
     if (batch <= 0) throw Error(MHTE_FAILED_PRECONDITION, "dense mlp: backward without a forward");
     const int64_t B = batch;
     const uint32_t Bu = uint32_t(B);
@@ -214,6 +216,13 @@ struct DenseMlp {
         }
       }
     }
+  }
+
+  // dy [B] -> SGD step on every layer; dx [B][w0] (fp32) when not null
+  void backward(const float* dy, float* dx, float lr, hipStream_t st) {
+    backward_chain(dy, dx, st);
+    const uint32_t Bu = uint32_t(batch);
+    const uint32_t KL = widths[nl];
     for (uint32_t l = 0; l < nl; ++l) {
       Layer& L = layers[l];
       const uint64_t n = uint64_t(L.N) * L.K;
@@ -223,6 +232,89 @@ struct DenseMlp {
     }
     mlp_sgd_vec_kernel<<<KL + 1, 256, 0, st>>>(w_last.p, b_last.p, part_last.p, Bu / 64, lr, KL);
     HIP_OK(hipGetLastError());
+  }
+
+  // The checks of backward_grads / load_params, on the host before any device call; the message names the entry
+  // point and the argument.  A pointer: not null when needed, 4-byte aligned.  A table: a host array of nl + 1
+  // such device pointers (GEMM layers, then the row-dot layer).
+  static void check_ptr(const char* op, const std::string& name, const void* p, bool needed) {
+    if (needed && !p) throw Error(MHTE_INVALID_ARGUMENT, std::string(op) + ": null argument: " + name);
+    if (reinterpret_cast<uintptr_t>(p) & 3u)
+      throw Error(MHTE_INVALID_ARGUMENT, std::string(op) + ": " + name + " must be 4-byte aligned");
+  }
+  template <class P>
+  void check_table(const char* op, const char* name, P const* table) const {
+    check_ptr(op, name, table, true);
+    for (uint32_t l = 0; l <= nl; ++l) check_ptr(op, std::string(name) + "[" + std::to_string(l) + "]", table[l], true);
+  }
+  void check_grads_call(float* const* wg, float* const* bg) const {
+    check_table("dense_mlp_backward_grads", "weight_grads", wg);
+    check_table("dense_mlp_backward_grads", "bias_grads", bg);
+    if (batch <= 0) throw Error(MHTE_FAILED_PRECONDITION, "dense mlp: backward without a forward");
+  }
+  void check_load_call(const float* const* w, const float* const* b) const {
+    check_table("dense_mlp_load_params", "weights", w);
+    check_table("dense_mlp_load_params", "biases", b);
+  }
+
+  // The backward chain, then the gradients of every layer out in ONE launch per kMlpTableLayers GEMM layers
+  // (mlp_export_grads_kernel; the row-dot layer's tree goes with the last one) instead of the SGD launches.
+  // No parameter changes; nothing waits, reads a device value or allocates.  (Arguments: check_grads_call.)
+  void backward_grads(const float* dy, float* dx, float* const* wg, float* const* bg, hipStream_t st) {
+    backward_chain(dy, dx, st);
+    for (uint32_t l0 = 0; l0 < nl; l0 += kMlpTableLayers) {
+      MlpExportArgs A{};
+      uint64_t e = 0;
+      const uint32_t l1 = std::min<uint32_t>(nl, l0 + kMlpTableLayers);
+      for (uint32_t l = l0; l < l1; ++l) {
+        const Layer& L = layers[l];
+        A.L[l - l0] = MlpExportLayer{L.slabs.p, L.db.p, wg[l], bg[l], e, L.N, L.K, L.split_now, 0};
+        e += uint64_t(L.N) * L.K;
+      }
+      A.n_layers = l1 - l0;
+      A.n_chunks = uint32_t(e / kMlpExportChunk);
+      uint32_t grid = A.n_chunks;
+      if (l1 == nl) {
+        A.part = part_last.p;
+        A.dw_last = wg[nl];
+        A.db_last = bg[nl];
+        A.nblk = uint32_t(batch / 64);
+        A.KL = widths[nl];
+        grid += A.KL + 1;
+      }
+      mlp_export_grads_kernel<<<grid, 256, 0, st>>>(A);
+      HIP_OK(hipGetLastError());
+    }
+  }
+
+  // Every layer's fp32 parameters from the caller's buffers into the masters and both bf16 copies: ONE launch
+  // per kMlpTableLayers GEMM layers (mlp_load_params_kernel; the row-dot layer goes with the last one).
+  // Nothing waits on the host: the sources must stay alive until the stream has passed the call.
+  // (Arguments: check_load_call.)
+  void load_params(const float* const* w, const float* const* b, hipStream_t st) {
+    for (uint32_t l0 = 0; l0 < nl; l0 += kMlpTableLayers) {
+      MlpLoadArgs A{};
+      uint64_t e = 0;
+      const uint32_t l1 = std::min<uint32_t>(nl, l0 + kMlpTableLayers);
+      for (uint32_t l = l0; l < l1; ++l) {
+        Layer& L = layers[l];
+        A.L[l - l0] = MlpLoadLayer{w[l], b[l], L.w.p, L.b.p, L.wb.p, L.wt.p, e, L.N, L.K};
+        e += uint64_t(L.N) * L.K;
+      }
+      A.n_layers = l1 - l0;
+      A.n_tiles = uint32_t(e / (kMlpLoadTile * kMlpLoadTile));
+      uint32_t grid = A.n_tiles;
+      if (l1 == nl) {
+        A.src_w_last = w[nl];
+        A.src_b_last = b[nl];
+        A.w_last = w_last.p;
+        A.b_last = b_last.p;
+        A.KL = widths[nl];
+        grid += (A.KL + 1 + 255) / 256;
+      }
+      mlp_load_params_kernel<<<grid, 256, 0, st>>>(A);
+      HIP_OK(hipGetLastError());
+    }
   }
 
   // flops of one forward + backward (+ the input gradient when asked for): 2 per multiply-add

@@ -506,5 +506,168 @@ __global__ __launch_bounds__(256) void mlp_refresh_kernel(const float* __restric
   wt[uint64_t(i % K) * N + uint32_t(i / K)] = h;
 }
 
+// ---- gradients out, parameters in (mhte_dense_mlp_backward_grads / _load_params): ALL layers in one launch.
+// The layers travel in the kernel arguments as a flat table, each entry with the element offset e0 of its
+// weights in the launch's numbering (ascending); a workgroup owns one chunk of that numbering and finds its
+// layer by a scan of e0[] (uniform over the workgroup: scalar loads of the argument block).  N and K are
+// multiples of 128, so a layer is a whole number of chunks and no chunk has a ragged end.  The workgroups behind
+// the last chunk serve the row-dot layer.  A tower deeper than kMlpTableLayers takes one launch per
+// kMlpTableLayers layers (the host cuts the table; the row-dot layer goes with the last launch).
+constexpr int kMlpTableLayers = 16;
+constexpr uint32_t kMlpExportChunk = 1024;   // weight-gradient elements per workgroup: 4 per thread
+constexpr uint32_t kMlpLoadTile = 64;        // weights per workgroup: a 64 x 64 tile (mlp_cast_transpose_kernel's)
+
+struct MlpExportLayer {
+  const float* slabs;   // [nsplit][N][K] split-K partials of dW
+  const float* db;      // [N]
+  float* dw;            // out [N][K]: 4-byte aligned; 16-byte accesses when 16-byte aligned
+  float* dbo;           // out [N]
+  uint64_t e0;
+  uint32_t N, K, nsplit, pad_;
+};
+struct MlpExportArgs {
+  MlpExportLayer L[kMlpTableLayers];
+  uint32_t n_layers, n_chunks;   // n_chunks: workgroups of the weight part (may be 0: the row-dot layer alone)
+  const float* part;             // [KL + 1][nblk] of mlp_last_bwd_kernel; KL = 0: no row-dot work in this launch
+  float* dw_last;                // out [KL]
+  float* db_last;                // out [1]
+  uint32_t nblk, KL;
+};
+struct MlpLoadLayer {
+  const float* src_w;   // [N][K] the caller's: 4-byte aligned; 16-byte loads when 16-byte aligned
+  const float* src_b;   // [N]
+  float* w;             // the masters and the two bf16 copies
+  float* b;
+  uint16_t* wb;
+  uint16_t* wt;
+  uint64_t e0;
+  uint32_t N, K;
+};
+struct MlpLoadArgs {
+  MlpLoadLayer L[kMlpTableLayers];
+  uint32_t n_layers, n_tiles;
+  const float* src_w_last;   // [KL]; KL = 0: no row-dot work in this launch
+  const float* src_b_last;   // [1]
+  float* w_last;
+  float* b_last;
+  uint32_t KL, pad_;
+};
+static_assert(sizeof(MlpExportArgs) < 4096 && sizeof(MlpLoadArgs) < 4096, "the argument block stays under 4 KB");
+
+// What mlp_sgd_kernel / mlp_sgd_vec_kernel compute as gsum / red[0], written out instead of applied:
+//   dw[i]   = ((+0 + slabs[0][i]) + slabs[1][i]) + ...  ascending over the nsplit slabs of THIS batch
+//   dbo[n]  = db[n]
+//   dw_last[k], db_last[0] = the per-thread strided sums of part[k][.] through the 256-wide tree
+// Thread t of a chunk owns elements 4 t .. 4 t + 3 with 16-byte accesses when dw is 16-byte aligned, elements
+// t + 256 j (j = 0..3) with 4-byte accesses otherwise: every element is one independent sum, the same bits.
+__global__ __launch_bounds__(256) void mlp_export_grads_kernel(MlpExportArgs A) {
+  __shared__ float red[256];
+  const uint32_t t = threadIdx.x;
+  if (blockIdx.x >= A.n_chunks) {   // the row-dot layer: one workgroup per element, KL = the bias
+    const uint32_t k = blockIdx.x - A.n_chunks;
+    if (A.KL == 0 || k > A.KL) return;
+    float s = 0.f;
+    for (uint32_t i = t; i < A.nblk; i += 256u) s += A.part[uint64_t(k) * A.nblk + i];
+    red[t] = s;
+    __syncthreads();
+    for (uint32_t o = 128; o >= 1; o >>= 1) {
+      if (t < o) red[t] += red[t + o];
+      __syncthreads();
+    }
+    if (t == 0) {
+      if (k < A.KL) A.dw_last[k] = red[0];
+      else A.db_last[0] = red[0];
+    }
+    return;
+  }
+  const uint64_t e = uint64_t(blockIdx.x) * kMlpExportChunk;
+  uint32_t l = 0;
+  while (l + 1 < A.n_layers && e >= A.L[l + 1].e0) ++l;
+  const uint64_t i0 = e - A.L[l].e0;   // the chunk's first element within the layer
+  const uint32_t N = A.L[l].N, nsplit = A.L[l].nsplit;
+  const uint64_t nk = uint64_t(N) * A.L[l].K;
+  const float* __restrict__ src = A.L[l].slabs + i0;
+  float* __restrict__ dst = A.L[l].dw + i0;
+  if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4   // (loads of four slabs in flight; the adds stay in slab order)
+    for (uint32_t s = 0; s < nsplit; ++s) {
+      const float4 v = *reinterpret_cast<const float4*>(src + uint64_t(s) * nk + 4u * t);
+      g.x += v.x;
+      g.y += v.y;
+      g.z += v.z;
+      g.w += v.w;
+    }
+    *reinterpret_cast<float4*>(dst + 4u * t) = g;
+  } else {
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (uint32_t s = 0; s < nsplit; ++s) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] += src[uint64_t(s) * nk + t + 256u * uint32_t(j)];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[t + 256u * uint32_t(j)] = g[j];
+  }
+  // the layer's first chunks carry its bias gradient as well (N K / 1024 chunks of 256 cover N: K >= 128)
+  const uint64_t n = i0 / kMlpExportChunk * 256u + t;
+  if (n < N) A.L[l].dbo[n] = A.L[l].db[n];
+}
+
+// The caller's fp32 parameters into the masters and both bf16 copies (f32_to_bf16, as mlp_refresh_kernel): one
+// 64 x 64 tile [n][k] of one layer per workgroup, through LDS as mlp_cast_transpose_kernel, so that W^T [K][N]
+// is written in 16-byte pieces of contiguous rows too (mlp_refresh_kernel's 2-byte stores N apart touch a
+// cache line per element).  The source takes 16-byte loads when 16-byte aligned, 4-byte loads of the same
+// elements otherwise.  The layer's first tiles copy its bias; the workgroups behind the last tile the row-dot
+// layer's vector and bias.
+__global__ __launch_bounds__(256) void mlp_load_params_kernel(MlpLoadArgs A) {
+  __shared__ uint16_t tile[64][72];   // [n][k]; 144-byte rows
+  const uint32_t t = threadIdx.x;
+  if (blockIdx.x >= A.n_tiles) {
+    const uint32_t i = (blockIdx.x - A.n_tiles) * 256u + t;
+    if (i < A.KL) A.w_last[i] = A.src_w_last[i];
+    else if (i == A.KL && A.KL) A.b_last[0] = A.src_b_last[0];
+    return;
+  }
+  const uint64_t e = uint64_t(blockIdx.x) * (kMlpLoadTile * kMlpLoadTile);
+  uint32_t l = 0;
+  while (l + 1 < A.n_layers && e >= A.L[l + 1].e0) ++l;
+  const uint32_t N = A.L[l].N, K = A.L[l].K;
+  const uint32_t tl = uint32_t((e - A.L[l].e0) / (kMlpLoadTile * kMlpLoadTile)), tiles_k = K / kMlpLoadTile;
+  const uint32_t n0 = tl / tiles_k * kMlpLoadTile, k0 = tl % tiles_k * kMlpLoadTile;
+  const float* __restrict__ src = A.L[l].src_w;
+  float* __restrict__ w = A.L[l].w;
+  uint16_t* __restrict__ wb = A.L[l].wb;
+  uint16_t* __restrict__ wt = A.L[l].wt;
+  const bool vec = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t p = t + uint32_t(i) * 256u, row = p >> 4, c4 = (p & 15u) * 4u;
+    const int64_t at = int64_t(n0 + row) * K + k0 + c4;
+    float4 v;
+    if (vec) v = *reinterpret_cast<const float4*>(src + at);
+    else v = make_float4(src[at], src[at + 1], src[at + 2], src[at + 3]);
+    *reinterpret_cast<float4*>(w + at) = v;
+    uint2 pk;
+    pk.x = uint32_t(f32_to_bf16(v.x)) | (uint32_t(f32_to_bf16(v.y)) << 16);
+    pk.y = uint32_t(f32_to_bf16(v.z)) | (uint32_t(f32_to_bf16(v.w)) << 16);
+    *reinterpret_cast<uint2*>(wb + at) = pk;
+    *reinterpret_cast<uint2*>(&tile[row][c4]) = pk;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t p = t + uint32_t(i) * 256u, krow = p >> 3, np = (p & 7u) * 8u;
+    uint32_t x[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      x[q] = uint32_t(tile[np + 2 * q][krow]) | (uint32_t(tile[np + 2 * q + 1][krow]) << 16);
+    *reinterpret_cast<uint4*>(wt + int64_t(k0 + krow) * N + n0 + np) = make_uint4(x[0], x[1], x[2], x[3]);
+  }
+  // (N / 64 * K / 64 tiles of 256 cover N: K >= 128)
+  const uint32_t n = tl * 256u + t;
+  if (n < N) A.L[l].b[n] = A.L[l].src_b[n];
+}
+
 }  // namespace mhte
 #endif  // MHTE_GEMM_KERNELS_H_

@@ -8,6 +8,21 @@ accumulation and SGD inside ``backward``.
   y = mlp.forward(x)                 # x [B, 1024] fp32 on the GPU -> y [B] fp32
   dx = mlp.backward(dy, lr=1e-3)     # dy [B] = dLoss/dy; SGD step on every layer; dx [B, 1024]
 
+With an optimizer outside the tower (data-parallel training, a clip over dense and sparse gradients together,
+the dense optimizers of ``monolith_amd.optimizers``) the gradients leave the tower and the parameters come
+back, one launch each for all layers (mhte_dense_mlp_backward_grads / mhte_dense_mlp_load_params):
+
+  variables = mlp.variables()                       # fp32 copies of the masters: the optimizer's variables
+  opt = optimizers.AdamomOptimizer(learning_rate=...)   # binds the variables at its first apply
+  # every step
+  y = mlp.forward(x)
+  dx, grads = mlp.backward_grads(dy)                # [dW_0, db_0, ..., dW_last, db_last]; no SGD
+  sparse_scale = feature_utils.clip_allreduce_and_apply(opt, zip(grads, variables), sparse_grads,
+                                                        clip_norm=..., use_allreduce=True)
+  mlp.load_params(variables)                        # masters and bf16 copies; does not synchronise
+
+``backward(dy, lr)`` from the same state leaves exactly ``p - lr * g`` for the exported ``g``.
+
 Widths (but the final 1) and batches are multiples of 128 (the GEMM tile).  No fallback: without the
 library or a GPU every call raises."""
 import ctypes as C
@@ -73,6 +88,66 @@ class DenseMlp:
                                                    device=self._device)
     _lib.check(self._lib.mhte_dense_mlp_backward(self._h, _lib.vp(dy), _lib.vp(dx), lr, self._stream()))
     return dx
+
+  def param_shapes(self):
+    """[(out, in), (out,)] per layer in the order of ``variables`` / ``backward_grads``: GEMM layers, then the
+    row-dot layer ((1, in), (1,))."""
+    shapes = []
+    for l in range(self.n_layers):
+      shapes += [(self.widths[l + 1], self.widths[l]), (self.widths[l + 1],)]
+    return shapes
+
+  def _checked(self, what, tensors):
+    """``tensors``: fp32, contiguous, on this device, with the numels of ``param_shapes`` -> the two pointer
+    tables (weights, biases) of the C ABI."""
+    shapes = self.param_shapes()
+    if not isinstance(tensors, (list, tuple)) or len(tensors) != len(shapes):
+      raise ValueError("%s: a list of %d tensors [W_0, b_0, ..., W_last, b_last], got %s" %
+                       (what, len(shapes), len(tensors) if isinstance(tensors, (list, tuple)) else type(tensors)))
+    for i, (t, s) in enumerate(zip(tensors, shapes)):
+      name = "%s[%d] (%s of layer %d)" % (what, i, "bias" if i % 2 else "weight", i // 2)
+      if not (isinstance(t, torch.Tensor) and t.device == self._device and t.dtype == torch.float32):
+        raise TypeError("%s must be a float32 tensor on %s" % (name, self._device))
+      if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+      n = s[0] * (s[1] if len(s) == 2 else 1)
+      if t.numel() != n:
+        raise ValueError("%s must have %d elements, got %d" % (name, n, t.numel()))
+    n = self.n_layers
+    return ((C.c_void_p * n)(*[t.data_ptr() for t in tensors[0::2]]),
+            (C.c_void_p * n)(*[t.data_ptr() for t in tensors[1::2]]))
+
+  def backward_grads(self, dy, need_dx=True, out=None, grads=None):
+    """The backward of ``backward`` WITHOUT the SGD step -> ``(dx, grads)``; ``grads`` =
+    ``[dW_0, db_0, ..., dW_last, db_last]`` (fp32, ``param_shapes``), new tensors unless given.  The
+    parameters keep their bits; ``backward(dy, lr)`` from the same state leaves ``p - lr * g``.  Given tensors
+    may be views into one flat buffer at ``distribution_ops.aligned_flat_offsets`` (the allreduce buffer)."""
+    assert dy.is_cuda and dy.dtype == torch.float32 and dy.is_contiguous() and dy.numel() == self._batch
+    if grads is None:
+      grads = [torch.empty(s, dtype=torch.float32, device=self._device) for s in self.param_shapes()]
+    wg, bg = self._checked("grads", grads)
+    dx = None
+    if need_dx:
+      dx = out if out is not None else torch.empty(self._batch, self.widths[0], dtype=torch.float32,
+                                                   device=self._device)
+    _lib.check(self._lib.mhte_dense_mlp_backward_grads(self._h, _lib.vp(dy), _lib.vp(dx), wg, bg, self._stream()))
+    return dx, list(grads)
+
+  def variables(self):
+    """A fresh list ``[W_0, b_0, ..., W_last, b_last]`` of fp32 COPIES of the master parameters: the variables
+    an optimizer owns (``load_params`` brings them back)."""
+    out = []
+    for l in range(self.n_layers):
+      out += list(self.get_params(l))
+    return out
+
+  def load_params(self, variables):
+    """All parameters from ``variables`` (the order and shapes of ``variables()``) into the masters and the bf16
+    copies, in one launch.  Does not synchronise: the list is kept until the next call, so that temporaries
+    stay alive; tensors the caller keeps must not change before the stream has passed the call."""
+    w, b = self._checked("variables", variables)
+    _lib.check(self._lib.mhte_dense_mlp_load_params(self._h, w, b, self._stream()))
+    self._loaded = list(variables)
 
   GEMM_ROLES = ("forward", "dgrad", "dgrad_input", "wgrad")
 

@@ -71,6 +71,19 @@ mhte_status mhte_dense_mlp_forward(mhte_dense_mlp* m, const float* x, int64_t ba
 mhte_status mhte_dense_mlp_backward(mhte_dense_mlp* m, const float* dy, float* dx, float lr, void* st) {
   return guard([&] { m->m.backward(dy, dx, lr, S(st)); });
 }
+mhte_status mhte_dense_mlp_backward_grads(mhte_dense_mlp* m, const float* dy, float* dx, float* const* wg,
+                                          float* const* bg, void* st) {
+  return guard([&] {
+    m->m.check_grads_call(wg, bg);
+    m->m.backward_grads(dy, dx, wg, bg, S(st));
+  });
+}
+mhte_status mhte_dense_mlp_load_params(mhte_dense_mlp* m, const float* const* w, const float* const* b, void* st) {
+  return guard([&] {
+    m->m.check_load_call(w, b);
+    m->m.load_params(w, b, S(st));
+  });
+}
 mhte_status mhte_dense_mlp_launch_counts(mhte_dense_mlp* m, int64_t out[8]) {
   return guard([&] {
     for (int r = 0; r < 4; ++r)
