@@ -2017,6 +2017,11 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_mstep_host.h"
 #include "mhte_shard_host.h"
 #include "mhte_gemm_host.h"
+#include "mhte_aux_host.h"
+#include "mhte_clip_host.h"
+#include "mhte_flat_host.h"
+#include "mhte_dense_opt_host.h"
+#include "mhte_ffm_host.h"
 
 struct mhte_multi_step {
   mhte::MultiStep ms;
@@ -2467,182 +2472,8 @@ mhte_status mhte_table_dump(mhte_multi_table* t, int32_t table, int64_t cap, int
 }
 
 // ---- post-exchange gather + pooling -------------------------------------------------------------
-extern "C++" {
+}  // extern "C"
 namespace mhte {
-// scratch of the deterministic (list-based) forms of the pooling ops: one per device, serialised
-struct AuxWs {
-  std::mutex mu;
-  DedupWs dd;
-  DevBuf<int64_t> keys, uids;
-  DevBuf<uint32_t> inverse, seg_off, seg_pos, nu;
-  DevBuf<float> clip_partials;   // clip by global norm (mhte_clip_host.h): the 1024 partial sums of squares
-  DevBuf<char> clip_table;       // ... and the tensor table of a call with more than 128 tensors
-  DevBuf<char> flat_table;       // aligned flat concat (mhte_flat_host.h): the same for its calls
-  DevBuf<char> dense_opt_table;  // dense optimizers (mhte_dense_opt_host.h): the same, beyond 96 variables
-  static AuxWs& of(int device) {
-    static std::mutex m;
-    static std::map<int, std::unique_ptr<AuxWs>> all;
-    std::lock_guard<std::mutex> g(m);
-    auto& p = all[device];
-    if (!p) {
-      p.reset(new AuxWs);
-      p->dd.device = device;
-    }
-    return *p;
-  }
-  // the scratch is reused by the next call in stream order; a call on ANOTHER stream is ordered behind
-  // the launches of the previous one by an event the stream waits for — the host never does (these
-  // ops sit between the forward and the backward of every training step: a host wait here drains the
-  // caller's queue once per step)
-  hipStream_t last = nullptr;
-  bool used = false;
-  hipEvent_t done = nullptr;
-  void enter(hipStream_t st) {
-    if (!done) HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    if (used && last != st) HIP_OK(hipStreamWaitEvent(st, done, 0));
-    last = st;
-    used = true;
-  }
-  void leave(hipStream_t st) { HIP_OK(hipEventRecord(done, st)); }   // after the call's last launch
-  // A stream that is being captured into a graph takes neither the wait nor the record: the graph's own
-  // edges order its launches, and an event the capture has touched must not be waited for by a later call
-  // outside it.  Whoever replays such a graph beside calls on another stream orders the two themselves.
-  struct Use {   // enter now, leave when the caller's launches are enqueued
-    AuxWs& ws;
-    hipStream_t st;
-    bool capturing = false;
-    Use(AuxWs& w, hipStream_t s) : ws(w), st(s) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-      capturing = cs == hipStreamCaptureStatusActive;
-      if (!capturing) ws.enter(st);
-    }
-    ~Use() {
-      if (!capturing) (void)hipEventRecord(ws.done, st);
-    }
-  };
-  // The same lists for keys known to lie in [0, 2^key_bits), key_bits <= 31: a STABLE radix sort of
-  // (key, position) pairs — equal keys keep their positions ascending — and the heads of the sorted runs
-  // compacted into uids / seg_off (csrc/mhte_group_kernels.h: this repo's own kernels since round 6; round 5
-  // went through rocPRIM's Onesweep sort + run-length encode + scan, ≈ 20 launches per grouping).  The
-  // list-building dedup below is a hash table with two device atomics per key and five launches over all n
-  // keys; the sort moves 8 bytes per key and pass and needs no atomic.  Keys come out ascending instead of
-  // in first-occurrence order; the consumers write one output row per key and do not care.  Keys outside
-  // the range are dropped, which is what the consumers did with them.  MHTE_GROUP_DD=1 selects the dedup
-  // form (A/B; read per call, so that a test can run both forms in one process).
-  DevBuf<uint32_t> k32b, gs_hist, gs_tot, gs_heads;
-  DevBuf<uint2> gs_kva, gs_kvb;
-  static bool use_sort() {
-    const char* e = getenv("MHTE_GROUP_DD");
-    return !(e && atoi(e) != 0);
-  }
-  void group_sorted(const int64_t* k, int64_t n, int key_bits, hipStream_t st) {
-    if (key_bits < 1) key_bits = 1;
-    if (!use_sort() || key_bits > 31 || n >= int64_t(0x7fffffff) || n < 1) {
-      group(k, n, st);
-      return;
-    }
-    uids.reserve(size_t(n) + 1);
-    seg_off.reserve(size_t(n) + 2);
-    seg_pos.reserve(size_t(n) + 1);
-    nu.reserve(4);
-    k32b.reserve(size_t(n));
-    const int bits = key_bits + 1;   // (`limit` = 2^key_bits itself is a key: the dropped ones, sorted last)
-    const int passes = (bits + kGsMaxBits - 1) / kGsMaxBits;
-    const int dig = (bits + passes - 1) / passes;
-    GsPass P{};
-    P.n = uint32_t(n);
-    P.limit = 1u << key_bits;
-    const uint64_t per_round = uint64_t(kGsWaves) * kGsRound;
-    P.rounds = uint32_t(std::max<uint64_t>(1, (uint64_t(n) + per_round * kGsMaxTiles - 1) / (per_round * kGsMaxTiles)));
-    const uint64_t tile_keys = per_round * P.rounds;
-    P.ntiles = uint32_t((uint64_t(n) + tile_keys - 1) / tile_keys);
-    P.tstride = (P.ntiles + 3u) & ~3u;
-    gs_hist.reserve(size_t(kGsMaxBins) * kGsMaxTiles);
-    gs_tot.reserve(kGsMaxBins);
-    P.hist = gs_hist.p;
-    P.tot = gs_tot.p;
-    if (passes > 1) gs_kva.reserve(size_t(n));
-    if (passes > 2) gs_kvb.reserve(size_t(n));
-    for (int j = 0; j < passes; ++j) {
-      P.shift = uint32_t(j * dig);
-      P.bits = uint32_t(std::min(dig, bits - j * dig));
-      // (key, position) words ping-pong between two buffers; the last pass writes the consumers' arrays
-      const bool last = j == passes - 1;
-      P.k64 = j == 0 ? k : nullptr;
-      P.kvin = j == 0 ? nullptr : ((j & 1) ? gs_kva.p : gs_kvb.p);
-      P.kvout = last ? nullptr : ((j & 1) ? gs_kvb.p : gs_kva.p);
-      P.kout = k32b.p;
-      P.pout = seg_pos.p;
-      gs_hist_kernel<<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
-      gs_rowscan_kernel<<<dim3(1u << P.bits), 64, 0, st>>>(P);
-      gs_scatter_kernel<<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
-    }
-    const uint32_t ntsel = uint32_t((uint64_t(n) + kGsSelTile - 1) / kGsSelTile);
-    gs_heads.reserve(ntsel);
-    gs_heads_count_kernel<<<dim3(ntsel), 1024, 0, st>>>(k32b.p, P.n, gs_heads.p);
-    gs_heads_emit_kernel<<<dim3(ntsel), 1024, 0, st>>>(k32b.p, P.n, P.limit, gs_heads.p, uids.p, seg_off.p, nu.p);
-    HIP_OK(hipGetLastError());
-  }
-  // distinct keys + their positions in ascending order -> uids / seg_off / seg_pos / nu
-  void group(const int64_t* k, int64_t n, hipStream_t st) {
-    uids.reserve(size_t(n) + 1);
-    inverse.reserve(size_t(n) + 1);
-    seg_off.reserve(size_t(n) + 2);
-    seg_pos.reserve(size_t(n) + 1);
-    nu.reserve(4);
-    dd.unique(k, n, uids.p, inverse.p, seg_off.p, seg_pos.p, nu.p, st);
-  }
-};
-// Small host arrays a call uploads (task tables, pointer tables): staged through a ring of pinned
-// buffers, so the H2D copy is asynchronous and no call waits for its stream; a slot is reused after
-// its copy has completed (the host waits only when kSlots calls are still in flight).
-struct PinnedStage {
-  static constexpr int kSlots = 8;
-  std::mutex mu;
-  char* buf[kSlots] = {};
-  size_t cap[kSlots] = {};
-  hipEvent_t ev[kSlots] = {};
-  bool pending[kSlots] = {};
-  int next = 0;
-  static PinnedStage& of(int device) {
-    static std::mutex m;
-    static std::map<int, std::unique_ptr<PinnedStage>> all;
-    std::lock_guard<std::mutex> g(m);
-    auto& p = all[device];
-    if (!p) p.reset(new PinnedStage);
-    return *p;
-  }
-  void upload(void* dst_dev, const void* src, size_t n, hipStream_t st) {
-    if (!n) return;
-    std::lock_guard<std::mutex> g(mu);
-    const int i = next;
-    next = (next + 1) % kSlots;
-    if (!ev[i]) HIP_OK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    if (pending[i]) HIP_OK(hipEventSynchronize(ev[i]));
-    if (cap[i] < n) {
-      if (buf[i]) HIP_OK(hipHostFree(buf[i]));
-      buf[i] = nullptr;
-      const size_t want = std::max<size_t>(n, size_t(1) << 16);
-      HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&buf[i]), want, hipHostMallocDefault));
-      cap[i] = want;
-    }
-    memcpy(buf[i], src, n);
-    HIP_OK(hipMemcpyAsync(dst_dev, buf[i], n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipEventRecord(ev[i], st));
-    pending[i] = true;
-  }
-};
-static bool pool_atomics() {   // MHTE_POOL_ATOMICS=1: the float-atomic forms (A/B runs)
-  static const bool on = getenv("MHTE_POOL_ATOMICS") != nullptr && atoi(getenv("MHTE_POOL_ATOMICS")) != 0;
-  return on;
-}
-static int current_device() {
-  int d = 0;
-  HIP_OK(hipGetDevice(&d));
-  return d;
-}
-
 // zeroed (gradient only): the caller has just filled `fused` with zeros — the first launch may store without
 // reading the destination
 template <bool GATHER>
@@ -2711,25 +2542,6 @@ static void fused_gather(float* fused, int32_t n_inputs, const int32_t* const* o
     HIP_OK(hipGetLastError());
   }
 }
-}  // namespace mhte
-#include "mhte_clip_host.h"
-#include "mhte_flat_host.h"
-#include "mhte_dense_opt_host.h"
-#include "mhte_ffm_host.h"
-}  // extern "C++"
-
-mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
-                                                  const int32_t* const* offsets, const int64_t* n,
-                                                  const int32_t* dims, float* const* outputs,
-                                                  void* stream) {
-  return guard([&] {
-    fused_gather<true>(const_cast<float*>(fused_embeddings), n_inputs, offsets, n, dims, outputs, 1.f,
-                       S(stream));
-  });
-}
-
-}  // extern "C"
-namespace mhte {
 // scale_dev != NULL: the factor is read on the device (scale is then not used)
 static void fused_gather_gradient(float* fused_grad, int64_t fused_len, int32_t n_inputs, const float* const* grads,
                                   const int32_t* const* offsets, const int64_t* n, const int32_t* dims, float scale,
@@ -2748,6 +2560,16 @@ static void fused_gather_gradient(float* fused_grad, int64_t fused_len, int32_t 
 }
 }  // namespace mhte
 extern "C" {
+
+mhte_status mhte_fused_gather_embeddings_by_input(const float* fused_embeddings, int32_t n_inputs,
+                                                  const int32_t* const* offsets, const int64_t* n,
+                                                  const int32_t* dims, float* const* outputs,
+                                                  void* stream) {
+  return guard([&] {
+    fused_gather<true>(const_cast<float*>(fused_embeddings), n_inputs, offsets, n, dims, outputs, 1.f,
+                       S(stream));
+  });
+}
 
 mhte_status mhte_fused_gather_embeddings_by_input_gradient(float* fused_grad, int64_t fused_len,
                                                            int32_t n_inputs,
@@ -2778,13 +2600,13 @@ mhte_status mhte_global_l2_reduce(const float* const* tensors, const int64_t* le
                                   float* result, void* stream) {
   return guard([&] {
     const char* op = "global_l2_reduce";
-    if (!tensors) clip_bad(op, "null argument: tensors");
-    if (!lens) clip_bad(op, "null argument: lens");
-    if (!result) clip_bad(op, "null argument: result");
+    if (!tensors) arg_bad(op, "null argument: tensors");
+    if (!lens) arg_bad(op, "null argument: lens");
+    if (!result) arg_bad(op, "null argument: result");
     clip_check(op, tensors, "tensors", nullptr, lens, n, true, clip_norm);
-    clip_need_device();
+    need_device();
     ClipTable T;
-    clip_build(T, op, tensors, nullptr, lens, n, false);
+    clip_entries(T, op, tensors, nullptr, lens, n, false);
     clip_norm_launch(T, clip_norm, result, /*fused=*/false, S(stream));
   });
 }
@@ -2793,15 +2615,15 @@ mhte_status mhte_clip_by_global_norm(const float* const* inputs, float* const* o
                                      int32_t n, float global_norm, float clip_norm, void* stream) {
   return guard([&] {
     const char* op = "clip_by_global_norm";
-    if (!inputs) clip_bad(op, "null argument: inputs");
-    if (!outputs) clip_bad(op, "null argument: outputs");
-    if (!lens) clip_bad(op, "null argument: lens");
+    if (!inputs) arg_bad(op, "null argument: inputs");
+    if (!outputs) arg_bad(op, "null argument: outputs");
+    if (!lens) arg_bad(op, "null argument: lens");
     clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
-    clip_need_device();
+    need_device();
     // clip_by_global_norm.h:42-43 on the host; not clipped: tensors that are in place take no part at all
     const float scale = global_norm > clip_norm ? clip_norm / global_norm : 1.0f;
     ClipTable T;
-    clip_build(T, op, inputs, outputs, lens, n, /*skip_inplace=*/scale == 1.0f);
+    clip_entries(T, op, inputs, outputs, lens, n, /*skip_inplace=*/scale == 1.0f);
     clip_scale_launch(T, kClipScaleArg, scale, nullptr, clip_norm, S(stream));
   });
 }
@@ -2810,14 +2632,14 @@ mhte_status mhte_clip_by_global_norm_dev(const float* const* inputs, float* cons
                                          int32_t n, const float* global_norm_dev, float clip_norm, void* stream) {
   return guard([&] {
     const char* op = "clip_by_global_norm_dev";
-    if (!inputs) clip_bad(op, "null argument: inputs");
-    if (!outputs) clip_bad(op, "null argument: outputs");
-    if (!lens) clip_bad(op, "null argument: lens");
-    if (!global_norm_dev) clip_bad(op, "null argument: global_norm_dev");
+    if (!inputs) arg_bad(op, "null argument: inputs");
+    if (!outputs) arg_bad(op, "null argument: outputs");
+    if (!lens) arg_bad(op, "null argument: lens");
+    if (!global_norm_dev) arg_bad(op, "null argument: global_norm_dev");
     clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
-    clip_need_device();
+    need_device();
     ClipTable T;
-    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_entries(T, op, inputs, outputs, lens, n, false);
     clip_scale_launch(T, kClipScaleNorm, 1.f, global_norm_dev, clip_norm, S(stream));
   });
 }
@@ -2826,14 +2648,14 @@ mhte_status mhte_clip_by_global_norm_fused(const float* const* inputs, float* co
                                            int32_t n, float clip_norm, float* result, void* stream) {
   return guard([&] {
     const char* op = "clip_by_global_norm_fused";
-    if (!inputs) clip_bad(op, "null argument: inputs");
-    if (!outputs) clip_bad(op, "null argument: outputs");
-    if (!lens) clip_bad(op, "null argument: lens");
-    if (!result) clip_bad(op, "null argument: result");
+    if (!inputs) arg_bad(op, "null argument: inputs");
+    if (!outputs) arg_bad(op, "null argument: outputs");
+    if (!lens) arg_bad(op, "null argument: lens");
+    if (!result) arg_bad(op, "null argument: result");
     clip_check(op, inputs, "inputs", outputs, lens, n, true, clip_norm);
-    clip_need_device();
+    need_device();
     ClipTable T;
-    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_entries(T, op, inputs, outputs, lens, n, false);
     clip_norm_launch(T, clip_norm, result, /*fused=*/true, S(stream));
   });
 }
@@ -2842,14 +2664,14 @@ mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* out
                                    int32_t n, const float* scale_dev, void* stream) {
   return guard([&] {
     const char* op = "scale_tensors_dev";
-    if (!inputs) clip_bad(op, "null argument: inputs");
-    if (!outputs) clip_bad(op, "null argument: outputs");
-    if (!lens) clip_bad(op, "null argument: lens");
-    if (!scale_dev) clip_bad(op, "null argument: scale_dev");
+    if (!inputs) arg_bad(op, "null argument: inputs");
+    if (!outputs) arg_bad(op, "null argument: outputs");
+    if (!lens) arg_bad(op, "null argument: lens");
+    if (!scale_dev) arg_bad(op, "null argument: scale_dev");
     clip_check(op, inputs, "inputs", outputs, lens, n, false, 0.f);
-    clip_need_device();
+    need_device();
     ClipTable T;
-    clip_build(T, op, inputs, outputs, lens, n, false);
+    clip_entries(T, op, inputs, outputs, lens, n, false);
     clip_scale_launch(T, kClipScaleWord, 1.f, scale_dev, 0.f, S(stream));
   });
 }
@@ -2858,11 +2680,9 @@ mhte_status mhte_scale_tensors_dev(const float* const* inputs, float* const* out
 mhte_status mhte_aligned_flat_offsets(const int64_t* lens, int32_t n, int32_t align_elems, int64_t* offsets) {
   return guard([&] {
     const char* op = "aligned_flat_offsets";
-    if (!lens) clip_bad(op, "null argument: lens");
-    if (!offsets) clip_bad(op, "null argument: offsets");
-    if (n < 0) clip_bad(op, "n must be >= 0, got " + std::to_string(n));
-    for (int32_t i = 0; i < n; ++i)
-      if (lens[i] < 0) clip_bad(op, "tensor " + std::to_string(i) + " has the negative length " + std::to_string(lens[i]));
+    if (!lens) arg_bad(op, "null argument: lens");
+    if (!offsets) arg_bad(op, "null argument: offsets");
+    check_lens(op, "tensor", lens, n);
     flat_check_align(op, align_elems);
     (void)flat_offsets(op, lens, n, align_elems, offsets);
   });
@@ -2873,19 +2693,19 @@ mhte_status mhte_aligned_flat_concat(const float* const* inputs, const int64_t* 
                                      void* stream) {
   return guard([&] {
     const char* op = "aligned_flat_concat";
-    if (!inputs) clip_bad(op, "null argument: inputs");
-    if (!lens) clip_bad(op, "null argument: lens");
+    if (!inputs) arg_bad(op, "null argument: inputs");
+    if (!lens) arg_bad(op, "null argument: lens");
     clip_check(op, inputs, "inputs", nullptr, lens, n, false, 0.f);
     flat_check_align(op, align_elems);
-    if (wire != 0 && wire != 1) clip_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
+    if (wire != 0 && wire != 1) arg_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
     const int64_t total = flat_offsets(op, lens, n, align_elems, nullptr);
     if (out_elems != total)
-      clip_bad(op, "out_elems must be the aligned total " + std::to_string(total) + ", got " + std::to_string(out_elems));
-    if (total && !out) clip_bad(op, "null argument: out");
-    if (!aligned16(out)) clip_bad(op, "out must be 16-byte aligned");
+      arg_bad(op, "out_elems must be the aligned total " + std::to_string(total) + ", got " + std::to_string(out_elems));
+    if (total && !out) arg_bad(op, "null argument: out");
+    if (!aligned16(out)) arg_bad(op, "out must be 16-byte aligned");
     FlatTable T;
-    flat_build(T, op, inputs, lens, n, align_elems);
-    clip_need_device();
+    flat_entries(T, op, inputs, lens, n, align_elems);
+    need_device();
     flat_concat_launch(T, scale, scale_dev, wire, out, S(stream));
   });
 }
@@ -2894,13 +2714,13 @@ mhte_status mhte_aligned_flat_decode(const void* flat, int32_t wire, int64_t tot
                                      void* stream) {
   return guard([&] {
     const char* op = "aligned_flat_decode";
-    if (total_elems < 0) clip_bad(op, "total_elems must be >= 0, got " + std::to_string(total_elems));
-    if (wire != 0 && wire != 1) clip_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
-    if (total_elems && !flat) clip_bad(op, "null argument: flat");
-    if (total_elems && !out) clip_bad(op, "null argument: out");
+    if (total_elems < 0) arg_bad(op, "total_elems must be >= 0, got " + std::to_string(total_elems));
+    if (wire != 0 && wire != 1) arg_bad(op, "wire must be 0 (fp32) or 1 (fp16), got " + std::to_string(wire));
+    if (total_elems && !flat) arg_bad(op, "null argument: flat");
+    if (total_elems && !out) arg_bad(op, "null argument: out");
     if (wire == 1 && total_elems && static_cast<const void*>(out) == flat)
-      clip_bad(op, "an fp16 flat buffer is not decoded in place");
-    clip_need_device();
+      arg_bad(op, "an fp16 flat buffer is not decoded in place");
+    need_device();
     flat_decode_launch(flat, wire, total_elems, post_scale, out, S(stream));
   });
 }
@@ -2917,7 +2737,7 @@ mhte_status mhte_dense_apply_adamom(float* const* vars, const int64_t* lens, int
                          grad_scale_dev, lr_dev, update_slots, use_v2};
     DenseOptTable T;
     dense_opt_check("dense_apply_adamom", q, /*c_needed=*/true, T);
-    clip_need_device();
+    need_device();
     const DenseOptHyper h{grad_scale, lr, ada_decay, mom_decay, epsilon, weight_decay};
     dense_opt_launch<kDenseAdamom>(T, q, h, S(stream));
   });
@@ -2933,7 +2753,7 @@ mhte_status mhte_dense_apply_rmsprop(float* const* vars, const int64_t* lens, in
                          grad_scale_dev, lr_dev, update_slots, use_v2};
     DenseOptTable T;
     dense_opt_check("dense_apply_rmsprop", q, /*c_needed=*/false, T);
-    clip_need_device();
+    need_device();
     if (!update_slots) return;   // (training_ops.cc:45, :66: without update_slots the op changes nothing)
     const DenseOptHyper h{grad_scale, lr, beta1, beta2, epsilon, weight_decay};
     dense_opt_launch<kDenseRmsprop>(T, q, h, S(stream));
@@ -2959,9 +2779,9 @@ mhte_status mhte_ffm_grad(const float* grad, int64_t grad_cols, const float* lef
 
 mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n) {
   return guard([&] {
-    if (!out) clip_bad("ffm_launch_counts", "null argument: out");
+    if (!out) arg_bad("ffm_launch_counts", "null argument: out");
     if (n != kFfmCounters)
-      clip_bad("ffm_launch_counts", "n must be " + std::to_string(kFfmCounters) + ", got " + std::to_string(n));
+      arg_bad("ffm_launch_counts", "n must be " + std::to_string(kFfmCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kFfmCounters; ++i) out[i] = g_ffm_launches[i].load(std::memory_order_relaxed);
   });
 }

@@ -8,7 +8,7 @@
 // is ONE FIXED TREE, a function of the tensors' contents and lengths alone — not of the grid, the device or
 // the run — and nothing comes back to the host:
 //   * every non-empty tensor is cut into chunks of 4096 consecutive floats (the last one short, read as if
-//     padded with +0), numbered in tensor order c = 0 .. C-1; a chunk never straddles two tensors;
+//     padded with +0), numbered in tensor order c = 0 .. C-1: the chunk table of mhte_chunk_table.h;
 //   * clip_partials_kernel, always 1024 workgroups of 256 threads: workgroup w takes chunks w, w + 1024, ...
 //     in that order; in a chunk thread t owns elements 4 * (256 * r + t) + k, r = 0..3, k = 0..3, and adds
 //     them into ONE accumulator that starts at +0 in (chunk, r, k) order, acc = acc + v * v with product and
@@ -23,11 +23,11 @@
 #ifndef MHTE_CLIP_KERNELS_H_
 #define MHTE_CLIP_KERNELS_H_
 
+#include "mhte_chunk_table.h"
 #include "mhte_kernels.h"
 
 namespace mhte {
 
-constexpr int kClipChunk = 4096;       // floats per chunk
 constexpr int kClipGroups = 1024;      // workgroups of the partials launch = number of partials
 constexpr int kClipThreads = 256;
 constexpr int kClipInline = 128;       // tensors in the kernel arguments; beyond: the table is uploaded per call
@@ -41,33 +41,9 @@ enum ClipScaleMode : int32_t {
   kClipScalePartials = 3,  // the partials of clip_partials_kernel, with clip_norm (the fused form)
 };
 
-// The non-empty tensors of a call: (pointers, length, first chunk).  EXT: the same arrays in device memory.
-struct ClipArgs {
-  const float* const* x_in;     // EXT
-  float* const* x_out;
-  const long long* x_len;
-  const uint32_t* x_chunk0;
-  uint32_t n_tensors, n_chunks;
-  const float* in[kClipInline];
-  float* out[kClipInline];       // (the partials launch does not read it)
-  long long len[kClipInline];
-  uint32_t chunk0[kClipInline];  // ascending; a tensor's chunks are chunk0[i] .. chunk0[i + 1] - 1
-};
-
-template <bool EXT>
-__device__ __forceinline__ uint32_t clip_chunk0(const ClipArgs& A, uint32_t i) {
-  return EXT ? ((const MHTE_GLOBAL uint32_t*)(A.x_chunk0))[i] : A.chunk0[i];
-}
-// the tensor that holds chunk c: the last one whose first chunk is <= c, searched in [lo, n_tensors)
-template <bool EXT>
-__device__ __forceinline__ uint32_t clip_tensor_of(const ClipArgs& A, uint32_t c, uint32_t lo) {
-  uint32_t hi = A.n_tensors - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (clip_chunk0<EXT>(A, mid) <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+// The non-empty tensors of a call: (in, out, length, first chunk); the partials launch does not read out.
+struct ClipArgs : ChunkArgs<kClipInline, 2, false> {};
+static_assert(sizeof(ClipArgs) + 6 * 8 < 4096, "the scale kernel's argument block stays under 4 KB");
 
 // One chunk's place, uniform over the workgroup.
 struct ClipChunk {
@@ -77,13 +53,11 @@ struct ClipChunk {
 };
 template <bool EXT>
 __device__ __forceinline__ ClipChunk clip_chunk_at(const ClipArgs& A, uint32_t c, uint32_t ti) {
-  const long long skip = (long long)(c - clip_chunk0<EXT>(A, ti)) * kClipChunk;
+  const long long skip = (long long)(c - tensor_chunk0<EXT>(A, ti)) * kChunkElems;
   ClipChunk k;
-  typedef const float* in_ptr;
-  typedef float* out_ptr;
-  const float* in = EXT ? ((const MHTE_GLOBAL in_ptr*)(A.x_in))[ti] : A.in[ti];
-  float* out = EXT ? ((const MHTE_GLOBAL out_ptr*)(A.x_out))[ti] : A.out[ti];
-  const long long len = EXT ? ((const MHTE_GLOBAL long long*)(A.x_len))[ti] : A.len[ti];
+  const float* in = chunk_ptr<EXT, const float>(A, 0, ti);
+  float* out = chunk_ptr<EXT, float>(A, 1, ti);
+  const long long len = chunk_len<EXT>(A, ti);
   k.in = in + skip;
   k.out = out ? out + skip : nullptr;
   k.rem = len - skip;
@@ -97,7 +71,7 @@ struct ClipRegs {
   float v[4][4];
 };
 __device__ __forceinline__ void clip_load(const ClipChunk& k, uint32_t t, ClipRegs& x) {
-  if (k.rem >= kClipChunk && (reinterpret_cast<uintptr_t>(k.in) & 15u) == 0) {
+  if (k.rem >= kChunkElems && (reinterpret_cast<uintptr_t>(k.in) & 15u) == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const clip_f32x4 q = *(const MHTE_GLOBAL clip_f32x4*)(k.in + 4 * (kClipThreads * r + int(t)));
@@ -137,19 +111,18 @@ template <bool EXT>
 __global__ __launch_bounds__(kClipThreads) void clip_partials_kernel(ClipArgs A, float* __restrict__ partials) {
   __shared__ float lds[kClipThreads];
   const uint32_t t = threadIdx.x, w = blockIdx.x;
-  const uint32_t C = A.n_chunks;
+  const uint32_t C = A.k.n_chunks;
   float acc = 0.f;
   if (w < C) {
     // the next chunk's loads travel while this chunk is added; the tensor index only moves forward
-    uint32_t ti = clip_tensor_of<EXT>(A, w, 0);
+    uint32_t ti = chunk_tensor_of<EXT>(A, w, 0);
     ClipRegs cur;
     clip_load(clip_chunk_at<EXT>(A, w, ti), t, cur);
     for (uint32_t c = w;; c += kClipGroups) {   // (C < 2^31, the host checks: c + 1024 does not wrap)
       const uint32_t cn = c + kClipGroups;
       ClipRegs nxt;
       if (cn < C) {
-        const uint32_t end = ti + 1 < A.n_tensors ? clip_chunk0<EXT>(A, ti + 1) : C;
-        if (cn >= end) ti = clip_tensor_of<EXT>(A, cn, ti + 1);
+        ti = chunk_advance<EXT>(A, ti, cn);
         clip_load(clip_chunk_at<EXT>(A, cn, ti), t, nxt);
       }
 #pragma unroll
@@ -219,13 +192,13 @@ __global__ __launch_bounds__(kClipThreads) void clip_scale_kernel(ClipArgs A, in
   }
   const bool one = scale == 1.0f;
   if (one && all_inplace) return;
-  const uint32_t C = A.n_chunks;
+  const uint32_t C = A.k.n_chunks;
   uint32_t ti = 0;
   for (uint32_t c = blockIdx.x; c < C; c += gridDim.x) {   // (C < 2^31: no wrap)
-    ti = clip_tensor_of<EXT>(A, c, ti);
+    ti = chunk_advance<EXT>(A, ti, c);
     const ClipChunk k = clip_chunk_at<EXT>(A, c, ti);
     if (one && k.in == k.out) continue;
-    if (k.rem >= kClipChunk && ((reinterpret_cast<uintptr_t>(k.in) | reinterpret_cast<uintptr_t>(k.out)) & 15u) == 0) {
+    if (k.rem >= kChunkElems && ((reinterpret_cast<uintptr_t>(k.in) | reinterpret_cast<uintptr_t>(k.out)) & 15u) == 0) {
       clip_f32x4 q[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) q[r] = *(const MHTE_GLOBAL clip_f32x4*)(k.in + 4 * (kClipThreads * r + int(t)));
@@ -241,7 +214,7 @@ __global__ __launch_bounds__(kClipThreads) void clip_scale_kernel(ClipArgs A, in
     }
     const MHTE_GLOBAL float* pi = (const MHTE_GLOBAL float*)(k.in);
     MHTE_GLOBAL float* po = (MHTE_GLOBAL float*)(k.out);
-    const long long n = k.rem < kClipChunk ? k.rem : (long long)kClipChunk;
+    const long long n = k.rem < kChunkElems ? k.rem : (long long)kChunkElems;
     for (long long e = t; e < n; e += kClipThreads) {
       const float x = pi[e];
       po[e] = one ? x : __fmul_rn(x, scale);

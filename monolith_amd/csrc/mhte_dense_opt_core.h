@@ -1,4 +1,5 @@
-// Dense optimizers, the arithmetic contract and the chunk table: one source for host and device.
+// Dense optimizers, the arithmetic contract and which variables enter the chunk table: one source for host and
+// device.
 // Reference: ResourceApplyAdamom (CPU only) and ResourceApplyRmsprop (V1 / V2, CPU and GPU),
 // native_training/optimizers/{adamom,rmsprop}.py, optimizers/cc/training_ops.cc and
 // optimizers/cc/kernels/training_ops{.h,.cc,_gpu.cu.cc} — the expression trees are those of
@@ -31,25 +32,13 @@
 #ifndef MHTE_DENSE_OPT_CORE_H_
 #define MHTE_DENSE_OPT_CORE_H_
 
-#include <stdint.h>
-
-#include <vector>
+#include "mhte_chunk_table.h"   // (MHTE_HD, and hip_runtime.h unless MHTE_HOST_ONLY)
 
 #if defined(MHTE_HOST_ONLY)
 #include <math.h>
-#ifndef MHTE_HD
-#define MHTE_HD
-#endif
-#else
-#include <hip/hip_runtime.h>
-#ifndef MHTE_HD
-#define MHTE_HD __host__ __device__ __forceinline__
-#endif
 #endif
 
 namespace mhte {
-
-constexpr int kDenseOptChunk = 4096;   // elements per chunk
 
 // one rounded product / sum (the build passes -ffp-contract=off; on the device the intrinsics say it again)
 MHTE_HD float dense_mul(float a, float b) {
@@ -116,40 +105,47 @@ MHTE_HD void dense_rmsprop_step(float& var, float& m, float& v, float g0, const 
 }
 
 // ---- the chunk table ----------------------------------------------------------------------------------
+constexpr int kDenseOptInline = 96;   // variables in the kernel arguments; beyond: the table is uploaded
+
 // Variable i owns [off[i], off[i] + len[i]) of every slot buffer (and of a flat gradient buffer), off[i] =
 // the sum of round_up(len[j], A) over j < i — the rule of mhte_aligned_flat_offsets, over ALL variables of
 // the optimizer.  A variable takes part in a call when it is not empty and, with the list source, has a
-// gradient; the ones that take part are cut into chunks of 4096 elements numbered in list order.
-struct DenseOptEntry {
-  float* var;
-  const float* grad;   // NULL with a flat source: the gradient lies at off in the flat buffer
-  long long len, off;
-  uint32_t chunk0;
-};
-// grads == NULL: the flat source.  -> false when the call has 2^31 or more chunks (the entries are then
+// gradient; the ones that take part enter the chunk table (mhte_chunk_table.h) in list order, each with the
+// pointers (var, gradient — NULL with a flat source: the gradient lies at off in the flat buffer).
+// grads == NULL: the flat source.  -> false when the call has 2^31 or more chunks (the table is then
 // incomplete).  The caller has checked n, lens and align_elems.
+template <class TABLE>
 inline bool dense_opt_table(float* const* vars, const float* const* grads, const int64_t* lens, int32_t n,
-                            int32_t align_elems, std::vector<DenseOptEntry>& entries, uint32_t* n_chunks) {
+                            int32_t align_elems, TABLE& T) {
   const long long mask = (long long)(align_elems) - 1;
-  uint64_t chunks = 0;
   long long off = 0;
-  entries.clear();
   for (int32_t i = 0; i < n; ++i) {
     const long long len = lens[i];
     if (len != 0 && (!grads || grads[i])) {
-      DenseOptEntry e;
-      e.var = vars[i];
-      e.grad = grads ? grads[i] : nullptr;
-      e.len = len;
-      e.off = off;
-      e.chunk0 = uint32_t(chunks);
-      entries.push_back(e);
-      chunks += (uint64_t(len) + kDenseOptChunk - 1) / kDenseOptChunk;
-      if (chunks >= (uint64_t(1) << 31)) return false;
+      const void* const p[2] = {vars[i], grads ? grads[i] : nullptr};
+      if (!T.add(p, len, off)) return false;
     }
     off += (len + mask) & ~mask;
   }
-  *n_chunks = uint32_t(chunks);
+  return true;
+}
+
+// The same table as a list of entries, for a caller that wants to look at it (tests/dense_opt_host_driver.cc).
+struct DenseOptEntry {
+  float* var;
+  const float* grad;   // NULL with a flat source
+  long long len, off;
+  uint32_t chunk0;
+};
+inline bool dense_opt_table(float* const* vars, const float* const* grads, const int64_t* lens, int32_t n,
+                            int32_t align_elems, std::vector<DenseOptEntry>& entries, uint32_t* n_chunks) {
+  ChunkTable<ChunkArgs<kDenseOptInline, 2, true>> T;
+  entries.clear();
+  if (!dense_opt_table(vars, grads, lens, n, align_elems, T)) return false;
+  for (uint32_t i = 0; i < T.A.k.n_tensors; ++i)
+    entries.push_back(DenseOptEntry{static_cast<float*>(T.ptr_at(0, i)), static_cast<const float*>(T.ptr_at(1, i)),
+                                    T.num_at(0, i), T.num_at(1, i), T.chunk0_at(i)});
+  *n_chunks = T.A.k.n_chunks;
   return true;
 }
 

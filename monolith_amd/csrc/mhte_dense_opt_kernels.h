@@ -4,10 +4,9 @@
 // arithmetic is mhte_dense_opt_core.h's; reference: ResourceApplyAdamom / ResourceApplyRmsprop,
 // native_training/optimizers/cc/kernels/training_ops{.cc,_gpu.cu.cc}.  Included by mhte.hip.
 //
-// The walk is flat_concat_kernel's (mhte_flat_kernels.h):
+// The walk is over the chunk table of mhte_chunk_table.h:
 //   * every variable that takes part is cut into chunks of 4096 elements, numbered in list order; the table
-//     gives (var pointer, gradient pointer or none, length, offset, chunk0) per variable; a chunk's variable
-//     is found by binary search over chunk0[];
+//     gives (var pointer, gradient pointer or none, length, offset, chunk0) per variable;
 //   * workgroups of 256 threads take chunks by grid stride; in a chunk thread t owns the four groups of 4
 //     elements at 4 * (256 * r + t), r = 0..3;
 //   * the slots m, v (and c) are flat fp32 buffers in the aligned layout: element k of variable i lives at
@@ -29,10 +28,9 @@
 namespace mhte {
 
 constexpr int kDenseOptThreads = 256;
-constexpr int kDenseOptInline = 96;          // variables in the kernel arguments; beyond: the table is uploaded
 constexpr int kDenseOptMaxGroups = 2048;     // workgroups at most (grid stride over the chunks)
 static_assert(kDenseOptInline == MHTE_DENSE_OPT_INLINE, "the public header states the kernel's constant");
-static_assert(kDenseOptChunk == 4 * 4 * kDenseOptThreads, "a thread owns four groups of 4 elements of a chunk");
+static_assert(kChunkElems == 4 * 4 * kDenseOptThreads, "a thread owns four groups of 4 elements of a chunk");
 #ifndef MHTE_DENSE_OPT_GROUPS
 #define MHTE_DENSE_OPT_GROUPS 1
 #endif
@@ -48,20 +46,9 @@ enum DenseOptKind : int { kDenseAdamom = 0, kDenseRmsprop = 1 };
 enum DenseOptSource : int { kDenseGradList = 0, kDenseGradFlat32 = 1, kDenseGradFlat16 = 2 };
 enum DenseOptFlags : int32_t { kDenseUpdateSlots = 1, kDenseV2 = 2 };
 
-// The variables of a call that take part.  EXT: the same arrays in device memory.
-struct DenseOptArgs {
-  float* const* x_var;          // EXT
-  const float* const* x_grad;
-  const long long* x_len;
-  const long long* x_off;
-  const uint32_t* x_chunk0;
-  uint32_t n_tensors, n_chunks;
-  float* var[kDenseOptInline];
-  const float* grad[kDenseOptInline];   // the list source; not read with a flat one
-  long long len[kDenseOptInline];
-  long long off[kDenseOptInline];
-  uint32_t chunk0[kDenseOptInline];     // ascending; a variable's chunks are chunk0[i] .. chunk0[i + 1] - 1
-};
+// The variables of a call that take part: (var, list gradient — not read with a flat source —, length, offset,
+// first chunk).
+struct DenseOptArgs : ChunkArgs<kDenseOptInline, 2, true> {};
 // the flat buffers of a call
 struct DenseOptBufs {
   float* m;
@@ -71,21 +58,6 @@ struct DenseOptBufs {
 };
 static_assert(sizeof(DenseOptArgs) + sizeof(DenseOptBufs) + sizeof(DenseOptHyper) + 2 * sizeof(void*) + 8 < 4096,
               "the kernel's argument block stays under 4 KB");
-
-template <bool EXT>
-__device__ __forceinline__ uint32_t dense_chunk0(const DenseOptArgs& A, uint32_t i) {
-  return EXT ? ((const MHTE_GLOBAL uint32_t*)(A.x_chunk0))[i] : A.chunk0[i];
-}
-// the variable that holds chunk c: the last one whose first chunk is <= c, searched in [lo, n_tensors)
-template <bool EXT>
-__device__ __forceinline__ uint32_t dense_tensor_of(const DenseOptArgs& A, uint32_t c, uint32_t lo) {
-  uint32_t hi = A.n_tensors - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (dense_chunk0<EXT>(A, mid) <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // One chunk's place, uniform over the workgroup.
 struct DenseChunk {
@@ -97,19 +69,17 @@ struct DenseChunk {
 };
 template <bool EXT, int SRC>
 __device__ __forceinline__ DenseChunk dense_chunk_at(const DenseOptArgs& A, uint32_t c, uint32_t ti) {
-  const long long skip = (long long)(c - dense_chunk0<EXT>(A, ti)) * kDenseOptChunk;
-  typedef float* var_ptr;
-  typedef const float* grad_ptr;
-  float* var = EXT ? ((const MHTE_GLOBAL var_ptr*)(A.x_var))[ti] : A.var[ti];
-  const long long len = EXT ? ((const MHTE_GLOBAL long long*)(A.x_len))[ti] : A.len[ti];
-  const long long off = EXT ? ((const MHTE_GLOBAL long long*)(A.x_off))[ti] : A.off[ti];
+  const long long skip = (long long)(c - tensor_chunk0<EXT>(A, ti)) * kChunkElems;
+  float* var = chunk_ptr<EXT, float>(A, 0, ti);
+  const long long len = chunk_len<EXT>(A, ti);
+  const long long off = chunk_off<EXT>(A, ti);
   DenseChunk k;
   k.var = var + skip;
   k.var_vec = (reinterpret_cast<uintptr_t>(k.var) & 15u) == 0;
   k.grad = nullptr;
   k.grad_vec = true;
   if constexpr (SRC == kDenseGradList) {
-    const float* grad = EXT ? ((const MHTE_GLOBAL grad_ptr*)(A.x_grad))[ti] : A.grad[ti];
+    const float* grad = chunk_ptr<EXT, const float>(A, 1, ti);
     k.grad = grad + skip;
     k.grad_vec = (reinterpret_cast<uintptr_t>(k.grad) & 15u) == 0;
   }
@@ -236,10 +206,10 @@ __global__ __launch_bounds__(kDenseOptThreads) void dense_opt_kernel(DenseOptArg
   const uint32_t t = threadIdx.x;
   if (grad_scale_dev) h.grad_scale = *(const MHTE_GLOBAL float*)(grad_scale_dev);
   if (lr_dev) h.lr = *(const MHTE_GLOBAL float*)(lr_dev);
-  const uint32_t C = A.n_chunks;
+  const uint32_t C = A.k.n_chunks;
   uint32_t c = blockIdx.x;
   if (c >= C) return;
-  uint32_t ti = dense_tensor_of<EXT>(A, c, 0);
+  uint32_t ti = chunk_tensor_of<EXT>(A, c, 0);
   DenseChunk kc = dense_chunk_at<EXT, SRC>(A, c, ti);
   int p = 0;
   DenseRegs<KIND> cur;
@@ -253,8 +223,7 @@ __global__ __launch_bounds__(kDenseOptThreads) void dense_opt_kernel(DenseOptArg
       const uint32_t cn = c + gridDim.x;
       more = cn < C;
       if (more) {
-        const uint32_t end = ti + 1 < A.n_tensors ? dense_chunk0<EXT>(A, ti + 1) : C;
-        if (cn >= end) ti = dense_tensor_of<EXT>(A, cn, ti + 1);
+        ti = chunk_advance<EXT>(A, ti, cn);
         kn = dense_chunk_at<EXT, SRC>(A, cn, ti);
         c = cn;
       }

@@ -1,5 +1,5 @@
 // Host side of the FFM feature cross (mhte_ffm_kernels.h): the checks of the entry points, the choice of form
-// (mhte_ffm_core.h), the launch and the launch counters.  Included by mhte.hip behind mhte_clip_host.h.
+// (mhte_ffm_core.h), the launch and the launch counters.  Included by mhte.hip behind mhte_aux_host.h.
 #ifndef MHTE_FFM_HOST_H_
 #define MHTE_FFM_HOST_H_
 
@@ -18,16 +18,16 @@ struct FfmShape {
 static inline bool ffm_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 static FfmShape ffm_check_shape(const char* op, int64_t left_cols, int64_t right_cols, int64_t batch,
                                 int32_t dim_size, int32_t int_type) {
-  if (batch < 0) clip_bad(op, "batch must be >= 0, got " + std::to_string(batch));
-  if (left_cols < 0) clip_bad(op, "left_cols must be >= 0, got " + std::to_string(left_cols));
-  if (right_cols < 0) clip_bad(op, "right_cols must be >= 0, got " + std::to_string(right_cols));
-  if (dim_size < 1) clip_bad(op, "dim_size must be >= 1, got " + std::to_string(dim_size));
+  if (batch < 0) arg_bad(op, "batch must be >= 0, got " + std::to_string(batch));
+  if (left_cols < 0) arg_bad(op, "left_cols must be >= 0, got " + std::to_string(left_cols));
+  if (right_cols < 0) arg_bad(op, "right_cols must be >= 0, got " + std::to_string(right_cols));
+  if (dim_size < 1) arg_bad(op, "dim_size must be >= 1, got " + std::to_string(dim_size));
   if (int_type != 0 && int_type != 1)
-    clip_bad(op, "int_type must be 0 (multiply) or 1 (dot), got " + std::to_string(int_type));
+    arg_bad(op, "int_type must be 0 (multiply) or 1 (dot), got " + std::to_string(int_type));
   const long long lim = (1ll << 31) - 1;
-  if (batch > lim) clip_bad(op, "batch must be below 2^31, got " + std::to_string(batch));
-  if (left_cols > lim) clip_bad(op, "left_cols must be below 2^31, got " + std::to_string(left_cols));
-  if (right_cols > lim) clip_bad(op, "right_cols must be below 2^31, got " + std::to_string(right_cols));
+  if (batch > lim) arg_bad(op, "batch must be below 2^31, got " + std::to_string(batch));
+  if (left_cols > lim) arg_bad(op, "left_cols must be below 2^31, got " + std::to_string(left_cols));
+  if (right_cols > lim) arg_bad(op, "right_cols must be below 2^31, got " + std::to_string(right_cols));
   FfmShape s;
   s.D = dim_size;
   s.L = left_cols / dim_size;
@@ -36,13 +36,13 @@ static FfmShape ffm_check_shape(const char* op, int64_t left_cols, int64_t right
   // L D and R D are below 2^31 each, so L R D is below 2^62
   s.lrd = s.L * s.R * s.D;
   if (s.lrd > lim)
-    clip_bad(op, "(left_cols / dim_size) * (right_cols / dim_size) * dim_size = " + std::to_string(s.lrd) +
-                     " overflows the kernels' 32-bit row index: left_cols, right_cols");
+    arg_bad(op, "(left_cols / dim_size) * (right_cols / dim_size) * dim_size = " + std::to_string(s.lrd) +
+                    " overflows the kernels' 32-bit row index: left_cols, right_cols");
   return s;
 }
 static void ffm_check_ptr(const char* op, const char* name, const void* p, bool needed) {
-  if (needed && !p) clip_bad(op, std::string("null argument: ") + name);
-  if (!ffm_aligned4(p)) clip_bad(op, std::string(name) + " must be 4-byte aligned");
+  if (needed && !p) arg_bad(op, std::string("null argument: ") + name);
+  if (!ffm_aligned4(p)) arg_bad(op, std::string(name) + " must be 4-byte aligned");
 }
 static inline bool ffm_ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -69,12 +69,12 @@ static void ffm_forward(const float* left, int64_t left_cols, const float* right
   const FfmShape s = ffm_check_shape(op, left_cols, right_cols, batch, dim_size, int_type);
   const long long want = s.dot ? s.L * s.R : s.lrd;
   if (out_cols != want)
-    clip_bad(op, "out_cols must be " + std::to_string(want) + " (" + (s.dot ? "L * R" : "L * R * dim_size") + "), got " +
-                     std::to_string(out_cols));
+    arg_bad(op, "out_cols must be " + std::to_string(want) + " (" + (s.dot ? "L * R" : "L * R * dim_size") + "), got " +
+                    std::to_string(out_cols));
   ffm_check_ptr(op, "left", left, batch > 0 && left_cols > 0);
   ffm_check_ptr(op, "right", right, batch > 0 && right_cols > 0);
   ffm_check_ptr(op, "out", out, batch > 0 && out_cols > 0);
-  clip_need_device();
+  need_device();
   if (batch == 0 || s.L == 0 || s.R == 0) return;
   // 16-byte accesses: left and right (staging loads), and out for multiply (dot stores single floats)
   const bool aligned = ffm_ptr16(left) && ffm_ptr16(right) && ((left_cols | right_cols) & 3) == 0 &&
@@ -96,18 +96,18 @@ static void ffm_gradient(const float* grad, int64_t grad_cols, const float* left
                          float* left_grad, float* right_grad, void* stream) {
   const char* op = "ffm_grad";
   const FfmShape s = ffm_check_shape(op, left_cols, right_cols, batch, dim_size, int_type);
-  if (grad_cols < 0) clip_bad(op, "grad_cols must be >= 0, got " + std::to_string(grad_cols));
-  if (grad_cols > (1ll << 31) - 1) clip_bad(op, "grad_cols must be below 2^31, got " + std::to_string(grad_cols));
+  if (grad_cols < 0) arg_bad(op, "grad_cols must be >= 0, got " + std::to_string(grad_cols));
+  if (grad_cols > (1ll << 31) - 1) arg_bad(op, "grad_cols must be below 2^31, got " + std::to_string(grad_cols));
   const long long feats = s.dot ? grad_cols : grad_cols / dim_size;
   if (feats != s.L * s.R)
-    clip_bad(op, "the in/out shape not match: grad_cols gives " + std::to_string(feats) + " features, left_cols and "
-                 "right_cols give " + std::to_string(s.L) + " * " + std::to_string(s.R));
+    arg_bad(op, "the in/out shape not match: grad_cols gives " + std::to_string(feats) + " features, left_cols and "
+                "right_cols give " + std::to_string(s.L) + " * " + std::to_string(s.R));
   ffm_check_ptr(op, "grad", grad, batch > 0 && grad_cols > 0);
   ffm_check_ptr(op, "left", left, batch > 0 && left_cols > 0);
   ffm_check_ptr(op, "right", right, batch > 0 && right_cols > 0);
   ffm_check_ptr(op, "left_grad", left_grad, batch > 0 && left_cols > 0);
   ffm_check_ptr(op, "right_grad", right_grad, batch > 0 && right_cols > 0);
-  clip_need_device();
+  need_device();
   if (batch == 0 || left_cols + right_cols == 0) return;
   hipStream_t st = S(stream);
   if (s.L == 0 || s.R == 0) {   // no term reaches any element: the reference's setZero is all there is

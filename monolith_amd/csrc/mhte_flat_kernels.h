@@ -7,12 +7,12 @@
 // [4, 1024]; [off[i], off[i] + len[i]) holds in[i][k] * scale — ONE fp32 product, rounded once, then (fp16
 // wire) one IEEE conversion to nearest-even — and [off[i] + len[i], off[i + 1]) holds +0 (the reference's
 // `out[id] = 0.0f`), whatever the scale is.  The reference's kernel walks the elements and looks every one up
-// in the offsets; here, as in mhte_clip_kernels.h:
+// in the offsets; here the walk is over the chunk table of mhte_chunk_table.h:
 //   * every non-empty tensor's OUTPUT span of round_up(len, A) elements is cut into chunks of 4096 elements,
 //     numbered in tensor order; a chunk never straddles two tensors, and a tensor's last chunk carries its
 //     padding (A divides 4096: a span has as many chunks as its tensor);
-//   * workgroups of 256 threads take chunks by grid stride; a chunk's tensor is found by binary search over
-//     chunk0[]; in a chunk thread t owns the four groups of 4 elements at 4 * (256 * r + t), r = 0..3;
+//   * workgroups of 256 threads take chunks by grid stride; in a chunk thread t owns the four groups of 4
+//     elements at 4 * (256 * r + t), r = 0..3;
 //   * the store side is always vector-aligned (out is 16-byte aligned, A >= 4): 16-byte stores for fp32,
 //     packed 8-byte stores for fp16; the load side takes 16-byte loads where the source pointer is 16-byte
 //     aligned and the group lies inside the tensor, 4-byte loads of the same elements otherwise (same bits);
@@ -26,41 +26,17 @@
 
 namespace mhte {
 
-constexpr int kFlatChunk = kClipChunk;     // output elements per chunk
 constexpr int kFlatThreads = kClipThreads;
 constexpr int kFlatInline = kClipInline;   // tensors in the kernel arguments; beyond: the table is uploaded per call
 constexpr int kFlatGroups = 2048;          // workgroups at most (grid stride over the chunks)
 constexpr int kFlatMinAlign = 4, kFlatMaxAlign = 1024;
 
-// The non-empty tensors of a call: (pointer, length, first output element, first chunk).  EXT: the same
-// arrays in device memory.
-struct FlatArgs {
-  const float* const* x_in;     // EXT
-  const long long* x_len;
-  const long long* x_off;
-  const uint32_t* x_chunk0;
-  uint32_t n_tensors, n_chunks;
-  uint32_t align_mask;          // A - 1
-  const float* in[kFlatInline];
-  long long len[kFlatInline];
-  long long off[kFlatInline];
-  uint32_t chunk0[kFlatInline];  // ascending; a tensor's chunks are chunk0[i] .. chunk0[i + 1] - 1
+// The non-empty tensors of a call: (pointer, length, first output element, first chunk), and A - 1.
+struct FlatCounts : ChunkCounts {
+  uint32_t align_mask;   // A - 1
 };
-
-template <bool EXT>
-__device__ __forceinline__ uint32_t flat_chunk0(const FlatArgs& A, uint32_t i) {
-  return EXT ? ((const MHTE_GLOBAL uint32_t*)(A.x_chunk0))[i] : A.chunk0[i];
-}
-// the tensor that holds chunk c: the last one whose first chunk is <= c, searched in [lo, n_tensors)
-template <bool EXT>
-__device__ __forceinline__ uint32_t flat_tensor_of(const FlatArgs& A, uint32_t c, uint32_t lo) {
-  uint32_t hi = A.n_tensors - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (flat_chunk0<EXT>(A, mid) <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+struct FlatArgs : ChunkArgs<kFlatInline, 1, true, FlatCounts> {};
+static_assert(sizeof(FlatArgs) + 4 * 8 < 4096, "the concat kernel's argument block stays under 4 KB");
 
 // One chunk's place, uniform over the workgroup.
 struct FlatChunk {
@@ -71,17 +47,16 @@ struct FlatChunk {
 };
 template <bool EXT>
 __device__ __forceinline__ FlatChunk flat_chunk_at(const FlatArgs& A, uint32_t c, uint32_t ti) {
-  const long long skip = (long long)(c - flat_chunk0<EXT>(A, ti)) * kFlatChunk;
-  typedef const float* in_ptr;
-  const float* in = EXT ? ((const MHTE_GLOBAL in_ptr*)(A.x_in))[ti] : A.in[ti];
-  const long long len = EXT ? ((const MHTE_GLOBAL long long*)(A.x_len))[ti] : A.len[ti];
-  const long long off = EXT ? ((const MHTE_GLOBAL long long*)(A.x_off))[ti] : A.off[ti];
+  const long long skip = (long long)(c - tensor_chunk0<EXT>(A, ti)) * kChunkElems;
+  const float* in = chunk_ptr<EXT, const float>(A, 0, ti);
+  const long long len = chunk_len<EXT>(A, ti);
+  const long long off = chunk_off<EXT>(A, ti);
   FlatChunk k;
   k.in = in + skip;
   k.out = off + skip;
   k.rem = len - skip;
-  const long long span = ((len + A.align_mask) & ~(long long)(A.align_mask)) - skip;
-  k.n_out = span < kFlatChunk ? int(span) : kFlatChunk;
+  const long long span = ((len + A.k.align_mask) & ~(long long)(A.k.align_mask)) - skip;
+  k.n_out = span < kChunkElems ? int(span) : kChunkElems;
   return k;
 }
 
@@ -146,10 +121,10 @@ __global__ __launch_bounds__(kFlatThreads) void flat_concat_kernel(FlatArgs A, i
   const uint32_t t = threadIdx.x;
   float scale = scale_arg;
   if (mode == kClipScaleWord) scale = *(const MHTE_GLOBAL float*)(src);
-  const uint32_t C = A.n_chunks;
+  const uint32_t C = A.k.n_chunks;
   uint32_t c = blockIdx.x;
   if (c >= C) return;
-  uint32_t ti = flat_tensor_of<EXT>(A, c, 0);
+  uint32_t ti = chunk_tensor_of<EXT>(A, c, 0);
   FlatChunk kc = flat_chunk_at<EXT>(A, c, ti);
   ClipRegs cur;
   flat_load(kc, t, cur);
@@ -158,8 +133,7 @@ __global__ __launch_bounds__(kFlatThreads) void flat_concat_kernel(FlatArgs A, i
     FlatChunk kn = kc;
     ClipRegs nxt;
     if (cn < C) {
-      const uint32_t end = ti + 1 < A.n_tensors ? flat_chunk0<EXT>(A, ti + 1) : C;
-      if (cn >= end) ti = flat_tensor_of<EXT>(A, cn, ti + 1);
+      ti = chunk_advance<EXT>(A, ti, cn);
       kn = flat_chunk_at<EXT>(A, cn, ti);
       flat_load(kn, t, nxt);
     }

@@ -145,6 +145,26 @@ def test_clip_beyond_the_inline_table_and_unaligned():
     np.testing.assert_array_equal(T.bits(o.cpu().numpy()), T.bits(e))
 
 
+@pytest.mark.parametrize("count", [128, 129])
+def test_clip_on_both_sides_of_the_inline_table_s_edge(count):
+  """128 tensors are the last list that rides in the kernel arguments, 129 the first that is uploaded: the fused
+  entry (norm and multiply) and the multiply alone with a host norm, 3000 elements each (one ragged chunk)."""
+  rng = np.random.default_rng(1000 + count)
+  hs = [rng.standard_normal(3000).astype(np.float32) for _ in range(count)]
+  clip_norm = 3.0
+  exp, norm_t = T.clip(hs, clip_norm)
+  assert np.isfinite(norm_t) and norm_t > clip_norm and all(np.isfinite(e).all() for e in exp)
+  ts = [dev(a) for a in hs]
+  outs, gn = clip_ops.clip_by_global_norm(ts, clip_norm)
+  assert T.bits(gn.cpu().numpy()) == T.bits(norm_t)
+  alone = clip_ops.clip_by_global_norm(ts, clip_norm, use_norm=float(norm_t))[0]
+  assert len(outs) == len(alone) == count
+  for o, a, e, t, h in zip(outs, alone, exp, ts, hs):
+    np.testing.assert_array_equal(T.bits(o.cpu().numpy()), T.bits(e))
+    np.testing.assert_array_equal(T.bits(a.cpu().numpy()), T.bits(e))
+    np.testing.assert_array_equal(T.bits(t.cpu().numpy()), T.bits(h))   # out of place: the inputs are left alone
+
+
 # ---- 3. in place --------------------------------------------------------------------------------------
 def test_in_place_same_bits_and_untouched_without_clipping():
   hs = host_set("edges")

@@ -198,6 +198,48 @@ def test_many_variables(count, kind, source):
   check_state(opt, tvars, model, "%d variables" % count)
 
 
+# ---- more chunks than workgroups --------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def long_vars():
+  """2052 chunks in front of 130 small variables: the launch has 2048 workgroups, so the first of them take a
+  second chunk — in the same variable, in the next one and in the one after."""
+  rng = np.random.default_rng(31)
+  return tuple([rng.standard_normal(n).astype(F32) for n in (2048 * 4096 + 5, 7, 4097)] + T.set_seeded(130, seed=130))
+
+
+@pytest.mark.parametrize("table", ["inline", "uploaded"])
+@pytest.mark.parametrize("kind,source", [("adamom", "list"), ("rmsprop_v2", "flat16")])
+def test_workgroups_take_a_second_chunk(kind, source, table):
+  hs = long_vars()[:3] if table == "inline" else long_vars()
+  missing = 1 if source == "list" else None   # a gradient missing in the middle: the variable behind keeps its offset
+  taking_part = len(hs) - (missing is not None)
+  assert (taking_part > _lib.DENSE_OPT_INLINE) == (table == "uploaded")
+  off = T.offsets([v.size for v in hs])
+  pad = np.ones(off[-1], bool)
+  for v, o in zip(hs, off):
+    pad[o:o + v.size] = False
+  opt = make_opt(kind)
+  planted = torch.full((off[-1],), FILL, dtype=torch.int32, device=DEV).view(torch.float32)
+  planted[dev(~pad)] = 0.0
+  state = {s: planted.clone() for s in opt.get_slot_names()}
+  state.update(numels=[v.size for v in hs], align=16)
+  opt.load_state_dict(state)
+  model = DT.Model(kind, hs)
+  tvars = [dev(v) for v in hs]
+  for grads in DT.seeded_grads([v.shape for v in hs], 2, seed=32):
+    grads = [None if i == missing else g for i, g in enumerate(grads)]
+    apply(opt, tvars, grads, source, scale=0.37)
+    model.step(as_seen(grads, source), grad_scale=0.37)
+  assert all(np.isfinite(v).all() for v in model.vars)
+  assert all(np.isfinite(x).all() for s in model.slots for x in model.slots[s])
+  check_state(opt, tvars, model, "%s %s, %s table" % (kind, source, table))
+  if missing is not None:
+    DT.assert_same_bits(tvars[missing].cpu().numpy(), hs[missing], "the variable without a gradient")
+  for s in opt.get_slot_names():
+    bits = opt.state_dict()[s].view(torch.int32).cpu().numpy()
+    assert (bits[pad] == FILL).all(), s
+
+
 # ---- None gradients, update_slots -------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", DT.KINDS)
 def test_none_gradients_leave_variable_and_slots_alone(kind):

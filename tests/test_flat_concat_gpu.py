@@ -111,6 +111,28 @@ def test_alignments(align, wire):
       np.testing.assert_array_equal(T.raw(b.cpu().numpy()), T.raw(a))
 
 
+# ---- more chunks than workgroups ------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def long_set():
+  """2052 chunks in front of 130 small tensors: the launch has 2048 workgroups, so workgroups 0 .. 3 take a
+  second chunk — workgroup 0's in the same tensor (its 5 tail elements and their padding), workgroup 1's in the
+  next one, those of 2 and 3 in the one after."""
+  rng = np.random.default_rng(23)
+  return [rng.standard_normal(n).astype(F32) for n in (2048 * 4096 + 5, 7, 4097)] + T.set_seeded(130, seed=130)
+
+
+@pytest.mark.parametrize("table", ["inline", "uploaded"])
+@pytest.mark.parametrize("wire", [F32, F16], ids=["fp32", "fp16"])
+def test_workgroups_take_a_second_chunk(wire, table):
+  hs = long_set()[:3] if table == "inline" else long_set()
+  assert sum((a.size + 4095) // 4096 for a in hs[:3]) == 2052 and (len(hs) > 128) == (table == "uploaded")
+  scale = np.float32(0.37)
+  assert np.isfinite(T.concat(hs[:3], scale, wire)).all()
+  got = check_concat(hs, [dev(a) for a in hs], scale, wire, scale_arg=dev(np.array(scale)))
+  tail = T.offsets([a.size for a in hs])[0] + hs[0].size
+  assert not T.raw(got[tail:tail + 11].cpu().numpy()).any()   # the 11 zeros behind the first tensor's 5 tail elements
+
+
 # ---- misaligned sources ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("wire", [F32, F16], ids=["fp32", "fp16"])
 def test_misaligned_sources_give_the_same_bits(wire):
