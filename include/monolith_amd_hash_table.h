@@ -529,6 +529,52 @@ mhte_status mhte_ffm_grad(const float* grad, int64_t grad_cols, const float* lef
                           float* left_grad, float* right_grad, void* stream);
 mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n);
 
+/* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
+ * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
+ * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split
+ * of DistributedMultiTypeHashTable (NT/distributed_ps.py:289-291, :497-499).  The ops are stable: inside a split
+ * the elements keep their input order (the reference's in-order loops; NT/distribution_ops_test.py:24-33, :67-87).
+ *
+ * mhte_split_plan (replaces the counting and placing loops, split_by_indices_op.cc:44-48, :66-70, :202-236):
+ *   indices [dev i64, n], each in [0, num_splits); num_splits in [1, 1024]; n below 2^31 - 1
+ *   pos     [dev i64, n]            the stable permutation, split after split: with off = the exclusive scan of
+ *                                   sizes, pos[off[s] .. off[s+1]) are the positions i with indices[i] == s,
+ *                                   ascending; the entries behind the last placed element are -1
+ *   sizes   [dev i64, num_splits]   the size of every split
+ *   n_bad   [dev i64, 1]            the indices outside [0, num_splits): counted here, placed in no split, never
+ *                                   the cause of a store outside the outputs
+ *   row_splits [host i64, n_row_splits] or NULL with n_row_splits 0: the boundaries of a ragged input (T + 1
+ *                                   entries, non-decreasing from 0 to n, else "The input ragged tensor is invalid.")
+ *   split_row_splits [dev i64, num_splits * n_row_splits]   entry [s][t]: the elements of split s whose position
+ *                                   is < row_splits[t] — the row_splits of split s (:224-230)
+ *   host_out [host i64, num_splits + num_splits * n_row_splits + 1] or NULL: sizes | split_row_splits | n_bad,
+ *                                   filled after synchronising the stream; with NULL the call waits for nothing
+ *   No atomic decides an order: the same input gives the same bits on every run.  One digit pass of the stable
+ *   group sort plus one finishing launch (4 launches; n == 0: none, the outputs are cleared).
+ * mhte_split_rows (replaces split_by_indices_op.cc:60-70): packed[q, :] = input[pos[q], :] for q < n; rows of
+ *   element_size >= 1 elements of elem_bytes 4 (float32) or 8 (int64); split s is the rows
+ *   packed[off[s] .. off[s+1]).  An entry of pos outside [0, n) (the -1 tail) moves nothing.
+ * mhte_split_rows_grad (replaces split_by_indices_op.cc:107-113): input_grads[pos[q], :] = grads[s][q - off[s], :]
+ *   for the placed q; grads is a HOST array of num_splits DEVICE pointers, split s being [sizes[s], element_size];
+ *   sizes [dev i64, num_splits] as the plan wrote them.  Rows whose index was out of range are not written.
+ * The movers accept any 4-byte-aligned buffer (pos and sizes: 8-byte); 16-byte accesses when a row is whole
+ * 16-byte words and every buffer is 16-byte aligned, else 4-byte ones — the same bits either way.  One launch
+ * per call, none for n == 0; n * element_size * elem_bytes / 4 must stay below 2^32.
+ * mhte_split_launch_counts: the launches of this process by form, n must be 6, index 0 rows / 4-byte form,
+ *   1 rows / 16-byte form, 2 gradient / 4-byte form, 3 gradient / 16-byte form, 4 plans that ran the partition,
+ *   5 those of them with row_splits.
+ * InvalidArgument, checked on the host before any device call: a null pointer for a needed operand, a misaligned
+ * pointer, a negative size, num_splits outside [1, 1024], invalid row_splits, an index overflow. */
+mhte_status mhte_split_plan(const int64_t* indices, int64_t n, int32_t num_splits, const int64_t* row_splits,
+                            int32_t n_row_splits, int64_t* pos, int64_t* sizes, int64_t* split_row_splits,
+                            int64_t* n_bad, int64_t* host_out, void* stream);
+mhte_status mhte_split_rows(const void* input, int64_t n, int64_t element_size, int32_t elem_bytes,
+                            const int64_t* pos, void* packed, void* stream);
+mhte_status mhte_split_rows_grad(const void* const* grads, const int64_t* sizes, int32_t num_splits, int64_t n,
+                                 int64_t element_size, int32_t elem_bytes, const int64_t* pos, void* input_grads,
+                                 void* stream);
+mhte_status mhte_split_launch_counts(int64_t* out, int32_t n);
+
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
  * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op

@@ -43,6 +43,7 @@
 #include "mhte_dense_opt_kernels.h"
 #include "mhte_ffm_kernels.h"
 #include "mhte_group_kernels.h"
+#include "mhte_split_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
 #include "mhte_mstep_kernels.h"
@@ -2022,6 +2023,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_flat_host.h"
 #include "mhte_dense_opt_host.h"
 #include "mhte_ffm_host.h"
+#include "mhte_split_host.h"
 
 struct mhte_multi_step {
   mhte::MultiStep ms;
@@ -2783,6 +2785,38 @@ mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n) {
     if (n != kFfmCounters)
       arg_bad("ffm_launch_counts", "n must be " + std::to_string(kFfmCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kFfmCounters; ++i) out[i] = g_ffm_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -----------------------------------
+mhte_status mhte_split_plan(const int64_t* indices, int64_t n, int32_t num_splits, const int64_t* row_splits,
+                            int32_t n_row_splits, int64_t* pos, int64_t* sizes, int64_t* split_row_splits,
+                            int64_t* n_bad, int64_t* host_out, void* stream) {
+  return guard([&] {
+    split_plan(indices, n, num_splits, row_splits, n_row_splits, pos, sizes, split_row_splits, n_bad, host_out,
+               stream);
+  });
+}
+
+mhte_status mhte_split_rows(const void* input, int64_t n, int64_t element_size, int32_t elem_bytes,
+                            const int64_t* pos, void* packed, void* stream) {
+  return guard([&] { split_rows(input, n, element_size, elem_bytes, pos, packed, stream); });
+}
+
+mhte_status mhte_split_rows_grad(const void* const* grads, const int64_t* sizes, int32_t num_splits, int64_t n,
+                                 int64_t element_size, int32_t elem_bytes, const int64_t* pos, void* input_grads,
+                                 void* stream) {
+  return guard([&] {
+    split_rows_grad(grads, sizes, num_splits, n, element_size, elem_bytes, pos, input_grads, stream);
+  });
+}
+
+mhte_status mhte_split_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    if (!out) arg_bad("split_launch_counts", "null argument: out");
+    if (n != kSplitCounters)
+      arg_bad("split_launch_counts", "n must be " + std::to_string(kSplitCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kSplitCounters; ++i) out[i] = g_split_launches[i].load(std::memory_order_relaxed);
   });
 }
 

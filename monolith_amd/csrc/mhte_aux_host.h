@@ -20,6 +20,8 @@ struct AuxWs {
   DevBuf<char> clip_table;       // ... and the tensor table of a call with more than 128 tensors
   DevBuf<char> flat_table;       // aligned flat concat (mhte_flat_host.h): the same for its calls
   DevBuf<char> dense_opt_table;  // dense optimizers (mhte_dense_opt_host.h): the same, beyond 96 variables
+  DevBuf<int64_t> split_row_splits;   // split by indices (mhte_split_host.h): the caller's row_splits
+  DevBuf<char> split_table;           // ... and the pointer table of its gradient
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;
@@ -77,6 +79,20 @@ struct AuxWs {
     const char* e = getenv("MHTE_GROUP_DD");
     return !(e && atoi(e) != 0);
   }
+  // the tiles of a pass over n keys (0 < n < 2^31) and its histogram scratch: at most kGsMaxTiles tiles, of one
+  // round of kGsRound keys per wavefront while that is enough
+  void gs_tiles(GsPass& P, int64_t n) {
+    P.n = uint32_t(n);
+    const uint64_t per_round = uint64_t(kGsWaves) * kGsRound;
+    P.rounds = uint32_t(std::max<uint64_t>(1, (uint64_t(n) + per_round * kGsMaxTiles - 1) / (per_round * kGsMaxTiles)));
+    const uint64_t tile_keys = per_round * P.rounds;
+    P.ntiles = uint32_t((uint64_t(n) + tile_keys - 1) / tile_keys);
+    P.tstride = (P.ntiles + 3u) & ~3u;
+    gs_hist.reserve(size_t(kGsMaxBins) * kGsMaxTiles);
+    gs_tot.reserve(kGsMaxBins);
+    P.hist = gs_hist.p;
+    P.tot = gs_tot.p;
+  }
   void group_sorted(const int64_t* k, int64_t n, int key_bits, hipStream_t st) {
     if (key_bits < 1) key_bits = 1;
     if (!use_sort() || key_bits > 31 || n >= int64_t(0x7fffffff) || n < 1) {
@@ -92,17 +108,8 @@ struct AuxWs {
     const int passes = (bits + kGsMaxBits - 1) / kGsMaxBits;
     const int dig = (bits + passes - 1) / passes;
     GsPass P{};
-    P.n = uint32_t(n);
     P.limit = 1u << key_bits;
-    const uint64_t per_round = uint64_t(kGsWaves) * kGsRound;
-    P.rounds = uint32_t(std::max<uint64_t>(1, (uint64_t(n) + per_round * kGsMaxTiles - 1) / (per_round * kGsMaxTiles)));
-    const uint64_t tile_keys = per_round * P.rounds;
-    P.ntiles = uint32_t((uint64_t(n) + tile_keys - 1) / tile_keys);
-    P.tstride = (P.ntiles + 3u) & ~3u;
-    gs_hist.reserve(size_t(kGsMaxBins) * kGsMaxTiles);
-    gs_tot.reserve(kGsMaxBins);
-    P.hist = gs_hist.p;
-    P.tot = gs_tot.p;
+    gs_tiles(P, n);
     if (passes > 1) gs_kva.reserve(size_t(n));
     if (passes > 2) gs_kvb.reserve(size_t(n));
     for (int j = 0; j < passes; ++j) {
@@ -115,9 +122,9 @@ struct AuxWs {
       P.kvout = last ? nullptr : ((j & 1) ? gs_kvb.p : gs_kva.p);
       P.kout = k32b.p;
       P.pout = seg_pos.p;
-      gs_hist_kernel<<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
+      gs_hist_kernel<false><<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
       gs_rowscan_kernel<<<dim3(1u << P.bits), 64, 0, st>>>(P);
-      gs_scatter_kernel<<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
+      gs_scatter_kernel<false><<<dim3(P.ntiles), kGsThreads, 0, st>>>(P);
     }
     const uint32_t ntsel = uint32_t((uint64_t(n) + kGsSelTile - 1) / kGsSelTile);
     gs_heads.reserve(ntsel);

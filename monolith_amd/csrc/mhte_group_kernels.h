@@ -48,6 +48,7 @@ struct GsPass {
   uint2* kvout;            // every pass but the last: (key, position) words
   uint32_t* kout;          // the last pass: sorted keys | their positions
   uint32_t* pout;
+  int64_t* pout64;         // the SPLIT form (mhte_split_host.h): the positions alone, as the int64 its callers index with
   uint32_t* hist;          // [bins][tstride]
   uint32_t* tot;           // [bins]
   uint32_t n, limit;
@@ -65,6 +66,9 @@ __device__ __forceinline__ uint2 gs_load(const GsPass& P, uint32_t i) {
   return P.kvin[i];
 }
 
+// SPLIT (one pass over the caller's keys, mhte_split_host.h): a key outside [0, limit) is no key at all — it is
+// neither counted nor placed, so `limit` needs no bin of its own and 1 024 splits fit the 10 bits of a pass.
+template <bool SPLIT>
 __global__ __launch_bounds__(kGsThreads) void gs_hist_kernel(GsPass P) {
   __shared__ uint32_t h[kGsMaxBins];
   const uint32_t bins = 1u << P.bits, mask = bins - 1u;
@@ -82,7 +86,8 @@ __global__ __launch_bounds__(kGsThreads) void gs_hist_kernel(GsPass P) {
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-      if (i0 + uint32_t(q) * kGsThreads < hi) atomicAdd(&h[(k[q] >> P.shift) & mask], 1u);
+      if (i0 + uint32_t(q) * kGsThreads < hi && (!SPLIT || k[q] != P.limit))
+        atomicAdd(&h[(k[q] >> P.shift) & mask], 1u);
   }
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < bins; b += kGsThreads) P.hist[size_t(b) * P.tstride + blockIdx.x] = h[b];
@@ -116,6 +121,40 @@ __global__ __launch_bounds__(64) void gs_rowscan_kernel(GsPass P) {
   if (lane == 63) P.tot[blockIdx.x] = incl;
 }
 
+// Where every bin starts in the output: binstart[b] = the exclusive scan of tot[0 .. bins) (<= 4 bins per thread),
+// by a whole workgroup of kGsThreads; wsum[w] is left as the sum of wavefront w's bins.  The caller synchronises
+// before it reads binstart.
+template <class T>
+__device__ __forceinline__ void gs_bin_starts(const T* __restrict__ tot, uint32_t bins, uint32_t* binstart,
+                                              uint32_t* wsum) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint32_t t4[kGsMaxBins / kGsThreads], s = 0;
+#pragma unroll
+  for (int q = 0; q < kGsMaxBins / kGsThreads; ++q) {
+    const uint32_t b = threadIdx.x * (kGsMaxBins / kGsThreads) + uint32_t(q);
+    t4[q] = b < bins ? uint32_t(tot[b]) : 0u;
+    s += t4[q];
+  }
+  uint32_t incl = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t x = __shfl_up(incl, o);
+    if (int(lane) >= o) incl += x;
+  }
+  if (lane == 63) wsum[w] = incl;
+  __syncthreads();
+  uint32_t run = incl - s;
+  for (uint32_t i = 0; i < w; ++i) run += wsum[i];
+#pragma unroll
+  for (int q = 0; q < kGsMaxBins / kGsThreads; ++q) {
+    const uint32_t b = threadIdx.x * (kGsMaxBins / kGsThreads) + uint32_t(q);
+    if (b < bins) binstart[b] = run;
+    run += t4[q];
+  }
+}
+
+template <bool SPLIT>
 __global__ __launch_bounds__(kGsThreads) void gs_scatter_kernel(GsPass P) {
   __shared__ uint32_t cur[kGsWaves][kGsMaxBins];   // digit counts of a wavefront, then its output cursors
   __shared__ uint32_t binstart[kGsMaxBins];
@@ -123,32 +162,7 @@ __global__ __launch_bounds__(kGsThreads) void gs_scatter_kernel(GsPass P) {
   const uint32_t bins = 1u << P.bits, mask = bins - 1u;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // ---- where every bin starts in the output: exclusive scan of tot[] (<= 4 bins per thread)
-  {
-    uint32_t t4[kGsMaxBins / kGsThreads], s = 0;
-#pragma unroll
-    for (int q = 0; q < kGsMaxBins / kGsThreads; ++q) {
-      const uint32_t b = threadIdx.x * (kGsMaxBins / kGsThreads) + uint32_t(q);
-      t4[q] = b < bins ? P.tot[b] : 0u;
-      s += t4[q];
-    }
-    uint32_t incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t x = __shfl_up(incl, o);
-      if (int(lane) >= o) incl += x;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t run = incl - s;
-    for (uint32_t i = 0; i < w; ++i) run += wsum[i];
-#pragma unroll
-    for (int q = 0; q < kGsMaxBins / kGsThreads; ++q) {
-      const uint32_t b = threadIdx.x * (kGsMaxBins / kGsThreads) + uint32_t(q);
-      if (b < bins) binstart[b] = run;
-      run += t4[q];
-    }
-  }
+  gs_bin_starts(P.tot, bins, binstart, wsum);
   for (uint32_t b = threadIdx.x; b < bins; b += kGsThreads) {
 #pragma unroll
     for (int x = 0; x < kGsWaves; ++x) cur[x][b] = 0;
@@ -171,7 +185,8 @@ __global__ __launch_bounds__(kGsThreads) void gs_scatter_kernel(GsPass P) {
     }
 #pragma unroll
     for (int it = 0; it < kGsIters; ++it)
-      if (base + uint32_t(it) * 64u < whi) atomicAdd(&cur[w][(k[it] >> P.shift) & mask], 1u);
+      if (base + uint32_t(it) * 64u < whi && (!SPLIT || k[it] != P.limit))
+        atomicAdd(&cur[w][(k[it] >> P.shift) & mask], 1u);
   }
   __syncthreads();
   // ---- counts -> cursors: bin start + what the tiles before this one hold + the wavefronts before this one
@@ -199,7 +214,7 @@ __global__ __launch_bounds__(kGsThreads) void gs_scatter_kernel(GsPass P) {
     }
 #pragma unroll
     for (int it = 0; it < kGsIters; ++it) {
-      const bool valid = base + uint32_t(it) * 64u < whi;
+      const bool valid = base + uint32_t(it) * 64u < whi && (!SPLIT || k[it] != P.limit);
       const uint32_t d = (k[it] >> P.shift) & mask;
       uint64_t peers = __ballot(valid);
       for (uint32_t b = 0; b < P.bits; ++b) {
@@ -212,7 +227,9 @@ __global__ __launch_bounds__(kGsThreads) void gs_scatter_kernel(GsPass P) {
         const uint32_t c = cur[w][d];
         if (below == 0) cur[w][d] = c + uint32_t(__popcll(peers));
         const uint32_t o = c + uint32_t(__popcll(below));
-        if (P.kvout) {
+        if constexpr (SPLIT) {
+          P.pout64[o] = int64_t(p[it]);
+        } else if (P.kvout) {
           P.kvout[o] = make_uint2(k[it], p[it]);
         } else {
           P.kout[o] = k[it];

@@ -1,0 +1,89 @@
+"""The parameter-server sharded table — host-side mirror of the raw-API branch of
+monolith/native_training/distributed_ps.py (``DistributedMultiTypeHashTable``: :282-338 lookup, :488-514
+apply_gradients).
+
+``num_ps`` local ``MultiHashTable``s stand in for the parameter servers, all on one device: the in-process PS
+cluster of the reference's own tests.  PS ``i`` owns the ids with ``floormod(id, num_ps) == i`` of every table.
+A call is the reference's sequence, op for op:
+
+  get_ragged_id -> unique_key_with_value_and_offset -> floormod(unique ids, num_ps) ->
+  ragged_split_by_indices -> per PS raw_lookup / raw_apply_gradients ->
+  fill_with_offset_map / fill_with_offset_map_gradient -> finalize_shared_tensor -> get_embeddings
+
+Out of scope: the transfer_float16 / non-raw branch, map_id_to_embedding, assign / assign_add /
+reinitialize through the shards.
+"""
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from monolith_amd import distribution_ops, entry
+from monolith_amd.multi_hash_table_ops import MultiHashTable
+
+
+class DistributedMultiTypeHashTable:
+  """reference distributed_ps.py:160-264: one multi-type hash table per PS, ids sharded by floormod."""
+
+  def __init__(self, num_ps: int, configs: Dict[str, entry.HashTableConfigInstance], name_suffix: str = "",
+               device: Optional[int] = None):
+    if not isinstance(num_ps, int) or isinstance(num_ps, bool) or num_ps < 1:
+      raise ValueError("DistributedMultiTypeHashTable: num_ps must be an int >= 1, got %r" % (num_ps,))
+    self._num_ps = num_ps
+    self._tables: List[MultiHashTable] = []
+    try:
+      for i in range(num_ps):
+        self._tables.append(MultiHashTable(configs, name_suffix="%s_ps%d" % (name_suffix, i), device=device))
+    except Exception:
+      self.close()
+      raise
+
+  def close(self):
+    for t in self._tables:
+      t.close()
+    self._tables = []
+
+  @property
+  def num_ps(self) -> int:
+    return self._num_ps
+
+  @property
+  def tables(self) -> Tuple[MultiHashTable, ...]:
+    """The per-PS tables, PS 0 first."""
+    return tuple(self._tables)
+
+  def _unique_and_split(self, slot_to_id, generate_buffer):
+    table_0 = self._tables[0]
+    dims = list(table_0.get_table_dim_sizes())
+    ragged_id = table_0.get_ragged_id(slot_to_id)
+    result = distribution_ops.unique_key_with_value_and_offset(ragged_id, dims, generate_buffer=generate_buffer)
+    index = torch.remainder(result.unique_key.values, self._num_ps)   # (floormod: a negative id's shard is >= 0)
+    splitted_ids, splitted_pos = distribution_ops.ragged_split_by_indices(index, result.unique_key, self._num_ps)
+    return dims, ragged_id, result, splitted_ids, splitted_pos
+
+  def lookup(self, slot_to_id: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """reference :282-338: the embeddings of ``slot_to_id``, one [len(ids), dim] tensor per given slot."""
+    dims, ragged_id, result, splitted_ids, splitted_pos = self._unique_and_split(slot_to_id, True)
+    filled_buffers = []
+    for i in range(self._num_ps):
+      flat_emb = self._tables[i].raw_lookup(splitted_ids[i])
+      filled_buffers.append(
+          distribution_ops.fill_with_offset_map(splitted_pos[i], flat_emb, result.value_offset,
+                                                result.value_offset_split, result.value_buffer, dims))
+    flat_emb = distribution_ops.finalize_shared_tensor(filled_buffers, dtype=torch.float32, shape=[None])
+    emb = self._tables[0].get_embeddings(ragged_id, flat_emb)
+    return {k: v for k, v in emb.items() if k in slot_to_id}
+
+  def apply_gradients(self, slot_to_id_and_grad: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
+                      global_step: int = 0, req_time: int = 0) -> "DistributedMultiTypeHashTable":
+    """reference :488-514: every unique id's gradients are summed (fill_with_offset_map_gradient) and applied on
+    the PS that owns the id."""
+    slot_to_id = {k: v[0] for k, v in slot_to_id_and_grad.items()}
+    slot_to_grad = {k: v[1] for k, v in slot_to_id_and_grad.items()}
+    dims, _, result, splitted_ids, splitted_pos = self._unique_and_split(slot_to_id, False)
+    flat_grad = self._tables[0].get_flat_value(slot_to_grad)
+    for i in range(self._num_ps):
+      splitted_flat_grad = distribution_ops.fill_with_offset_map_gradient(
+          splitted_pos[i], flat_grad, result.value_offset, result.value_offset_split, dims)
+      self._tables[i].raw_apply_gradients(splitted_ids[i], splitted_flat_grad, global_step=global_step,
+                                          req_time=req_time)
+    return self

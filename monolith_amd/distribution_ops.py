@@ -702,3 +702,208 @@ def aligned_flat_split(like, flat: torch.Tensor, post_scale: Optional[float] = N
                                               1.0 if post_scale is None else float(post_scale), vp(dst), _stream()))
     flat = dst
   return [flat[o:o + _numel_of(s)].view(s) for o, s in zip(offs, shapes)]
+
+
+# ---- split by indices: the shard split of the parameter-server path --------------------------------------
+# (reference distribution_ops.py:27-78, :175-190; runtime/ops/split_by_indices_op.cc:28-118, :188-243)
+# mhte_split_launch_counts' order
+SPLIT_COUNTER_NAMES = ("rows/vec1", "rows/vec4", "gradient/vec1", "gradient/vec4", "plan", "plan/ragged")
+_SPLIT_ELEM_BYTES = {torch.float32: 4, torch.int64: 8}
+
+
+class SplitPlan(NamedTuple):
+  pos: torch.Tensor                         # int64 [n]: the stable permutation, split after split; -1 behind the last
+  sizes: torch.Tensor                       # int64 [num_splits]
+  split_row_splits: Optional[torch.Tensor]  # int64 [num_splits, T + 1] when row_splits were given
+  n_bad: torch.Tensor                       # int64 [1]: the indices outside [0, num_splits)
+
+
+def split_launch_counts():
+  """{form: launches of this process} (mhte_split_launch_counts): which mover ran, how many plans."""
+  out = (C.c_int64 * len(SPLIT_COUNTER_NAMES))()
+  check(_lib.lib().mhte_split_launch_counts(out, len(SPLIT_COUNTER_NAMES)))
+  return dict(zip(SPLIT_COUNTER_NAMES, [int(x) for x in out]))
+
+
+def _split_indices(what, indices, num_splits):
+  if not isinstance(num_splits, int) or isinstance(num_splits, bool):
+    raise TypeError("%s: num_splits must be an int, got %r" % (what, num_splits))
+  if not isinstance(indices, torch.Tensor):
+    raise TypeError("%s: indices must be a torch tensor, got %s" % (what, type(indices).__name__))
+  if indices.dtype != torch.int64:
+    raise TypeError("%s: indices must be int64, got %s" % (what, indices.dtype))
+  if not indices.is_cuda:
+    raise TypeError("%s: indices must be on the GPU (there is no CPU path)" % what)
+  return indices.reshape(-1).contiguous()
+
+
+def _checked_row_splits(row_splits, n):
+  rs = np.ascontiguousarray(row_splits, dtype=np.int64).reshape(-1)
+  if rs.size < 1 or rs[0] != 0 or rs[-1] != n or (np.diff(rs) < 0).any():
+    raise _lib.InvalidArgumentError(_lib.MHTE_INVALID_ARGUMENT, "The input ragged tensor is invalid.")
+  return rs
+
+
+def _plan(indices, num_splits, row_splits, want_host):
+  """-> (SplitPlan, host array sizes | split_row_splits | n_bad or None); ``indices`` checked and flat."""
+  n, dev = indices.numel(), indices.device
+  R = 0 if row_splits is None else row_splits.size
+  pos = torch.empty(n, dtype=torch.int64, device=dev)
+  sizes = torch.empty(max(num_splits, 0), dtype=torch.int64, device=dev)
+  srs = torch.empty((max(num_splits, 0), R), dtype=torch.int64, device=dev) if R else None
+  n_bad = torch.empty(1, dtype=torch.int64, device=dev)
+  host = np.empty(max(num_splits, 0) * (1 + R) + 1, dtype=np.int64) if want_host else None
+  with torch.cuda.device(dev):
+    check(_lib.lib().mhte_split_plan(vp(indices), n, num_splits,
+                                     None if row_splits is None else row_splits.ctypes.data_as(C.c_void_p), R,
+                                     vp(pos), vp(sizes), vp(srs), vp(n_bad),
+                                     None if host is None else host.ctypes.data_as(C.c_void_p), _stream()))
+  return SplitPlan(pos, sizes, srs, n_bad), host
+
+
+def split_plan(indices: torch.Tensor, num_splits: int, row_splits=None) -> SplitPlan:
+  """The partition behind ``split_by_indices`` / ``ragged_split_by_indices`` with everything left on the device
+  (mhte_split_plan): nothing is read back and nothing waits, for callers who chain on the stream.  ``row_splits``:
+  the host boundaries of a ragged input; the plan then carries every split's row_splits as a device table."""
+  indices = _split_indices("split_plan", indices, num_splits)
+  rs = None if row_splits is None else _checked_row_splits(row_splits, indices.numel())
+  return _plan(indices, num_splits, rs, False)[0]
+
+
+def _bad_indices(what, n_bad, num_splits):
+  if n_bad:
+    raise _lib.InvalidArgumentError(
+        _lib.MHTE_INVALID_ARGUMENT, "%s: %d indices are outside [0, %d)" % (what, n_bad, num_splits))
+
+
+def _move_rows(tensor, pos):
+  """packed[q] = tensor[pos[q]] (mhte_split_rows); ``tensor`` contiguous, its first dim = len(pos)."""
+  n = pos.numel()
+  packed = torch.empty_like(tensor)
+  if n:
+    with torch.cuda.device(tensor.device):
+      check(_lib.lib().mhte_split_rows(vp(tensor), n, tensor.numel() // n, _SPLIT_ELEM_BYTES[tensor.dtype], vp(pos),
+                                       vp(packed), _stream()))
+  return packed
+
+
+def _cut(packed, sizes):
+  out, off = [], 0
+  for s in sizes:
+    out.append(packed[off:off + int(s)])
+    off += int(s)
+  return out
+
+
+def _split_forward(indices, tensor, num_splits):
+  what = "split_by_indices"
+  indices = _split_indices(what, indices, num_splits)
+  if not isinstance(tensor, torch.Tensor):
+    raise TypeError("%s: tensor must be a torch tensor, got %s" % (what, type(tensor).__name__))
+  if tensor.dtype not in _SPLIT_ELEM_BYTES:
+    raise TypeError("%s: tensor must be float32 or int64, got %s" % (what, tensor.dtype))
+  if not tensor.is_cuda:
+    raise TypeError("%s: tensor must be on the GPU (there is no CPU path)" % what)
+  if tensor.device != indices.device:
+    raise ValueError("%s: tensor is on %s, indices on %s" % (what, tensor.device, indices.device))
+  n = indices.numel()
+  if tensor.dim() < 1 or tensor.shape[0] != n or (n and tensor.numel() == 0):
+    raise ValueError("%s: tensor must hold one non-empty element per index: shape %s, %d indices" %
+                     (what, tuple(tensor.shape), n))
+  tensor = tensor if tensor.is_contiguous() else tensor.contiguous()
+  plan, host = _plan(indices, num_splits, None, True)
+  _bad_indices(what, int(host[-1]), num_splits)
+  sizes = [int(s) for s in host[:num_splits]]
+  return _cut(_move_rows(tensor, plan.pos), sizes), plan, sizes
+
+
+class _SplitByIndices(torch.autograd.Function):
+  """reference distribution_ops.py:37-43: the registered gradient is MonolithSplitByIndicesGradient."""
+
+  @staticmethod
+  def forward(ctx, indices, tensor, num_splits):
+    splits, plan, sizes = _split_forward(indices, tensor, num_splits)
+    ctx.save_for_backward(plan.pos, plan.sizes)
+    ctx.sizes, ctx.shape = sizes, tuple(tensor.shape)
+    return tuple(splits)
+
+  @staticmethod
+  def backward(ctx, *grads):
+    pos, sizes_dev = ctx.saved_tensors
+    n, shape = pos.numel(), ctx.shape
+    out = torch.empty(shape, dtype=torch.float32, device=pos.device)
+    if n == 0:
+      return None, out, None
+    gs = []
+    for g, s in zip(grads, ctx.sizes):
+      want = (s,) + shape[1:]
+      if g is None:
+        g = torch.zeros(want, dtype=torch.float32, device=pos.device)
+      if tuple(g.shape) != want:
+        raise ValueError("split_by_indices: a gradient of shape %s for a split of shape %s" % (tuple(g.shape), want))
+      gs.append(g.to(dtype=torch.float32).contiguous())
+    with torch.cuda.device(pos.device):
+      check(_lib.lib().mhte_split_rows_grad(_ptr_array(gs), vp(sizes_dev), len(gs), n, out.numel() // n, 4, vp(pos),
+                                            vp(out), _stream()))
+    return None, out, None
+
+
+def split_by_indices(indices: torch.Tensor, tensor: torch.Tensor, num_splits: int) -> List[torch.Tensor]:
+  """reference distribution_ops.py:27-34 (MonolithSplitByIndices, split_by_indices_op.cc:28-75): split the elements
+  of ``tensor`` (float32 or int64, one per index along its first dim, any trailing shape) into ``num_splits``
+  tensors by ``indices``; inside a split the elements keep their input order.  The results are views of one
+  packed buffer.  A float32 tensor is differentiable (MonolithSplitByIndicesGradient).  The sizes come back to
+  the host, which is where the shapes of the results live; an index outside [0, num_splits) is an
+  InvalidArgumentError."""
+  if isinstance(tensor, torch.Tensor) and tensor.dtype == torch.float32:
+    return list(_SplitByIndices.apply(indices, tensor, num_splits))
+  return _split_forward(indices, tensor, num_splits)[0]
+
+
+def ragged_split_by_indices(indices: torch.Tensor, num: Ragged,
+                            num_splits: int) -> Tuple[List[Ragged], List[Ragged]]:
+  """reference distribution_ops.py:46-78 (MonolithRaggedSplitByIndices, split_by_indices_op.cc:188-243): split an
+  int64 ragged tensor into ``num_splits`` ragged tensors by ``indices``; returns the split ragged tensors and the
+  original position of every number.  For example,
+    indices = [0, 1, 0, 1], num = [[4, 3, 2], [1]], num_splits = 2
+    ===> [[[4, 2], []], [[3], [1]]],  [[[0, 2], []], [[1], [3]]]
+  Values and positions stay on the device; every split's row_splits is on the host."""
+  what = "ragged_split_by_indices"
+  indices = _split_indices(what, indices, num_splits)
+  values = num.values
+  if not (isinstance(values, torch.Tensor) and values.dtype == torch.int64 and values.is_cuda):
+    raise TypeError("%s: num.values must be an int64 tensor on the GPU (there is no CPU path)" % what)
+  values = values.reshape(-1).contiguous()
+  if values.numel() != indices.numel():
+    raise _lib.InvalidArgumentError(
+        _lib.MHTE_INVALID_ARGUMENT, "Ragged tensor values size must match indices size. Got %d v.s. %d" %
+        (values.numel(), indices.numel()))
+  rs = _checked_row_splits(num.row_splits, indices.numel())
+  plan, host = _plan(indices, num_splits, rs, True)
+  _bad_indices(what, int(host[-1]), num_splits)
+  sizes = [int(s) for s in host[:num_splits]]
+  table = host[num_splits:num_splits + num_splits * rs.size].reshape(num_splits, rs.size)
+  vals, poss = _cut(_move_rows(values, plan.pos), sizes), _cut(plan.pos, sizes)
+  splits = [np.ascontiguousarray(table[s]) for s in range(num_splits)]
+  return ([Ragged(v, r) for v, r in zip(vals, splits)], [Ragged(p, r) for p, r in zip(poss, splits)])
+
+
+def finalize_shared_tensor(shared_tensor_handles: List[torch.Tensor], dtype=None, shape=None) -> torch.Tensor:
+  """reference distribution_ops.py:175-190: the shared buffer the fills wrote into.  ``fill_with_offset_map``
+  returns the buffer it was given, so the handles must all be that one tensor (the *same handle* repeated); the
+  list only carries the fills' order.  ``dtype`` / ``shape`` (None entries: unknown) are checked against it."""
+  if not isinstance(shared_tensor_handles, (list, tuple)) or not shared_tensor_handles:
+    raise ValueError("finalize_shared_tensor: needs a non-empty list of handles")
+  first = shared_tensor_handles[0]
+  for h in shared_tensor_handles:
+    if not isinstance(h, torch.Tensor):
+      raise TypeError("finalize_shared_tensor: a handle must be a torch tensor, got %s" % type(h).__name__)
+    if (h.data_ptr() != first.data_ptr() or h.numel() != first.numel() or h.dtype != first.dtype or
+        h.device != first.device):
+      raise _lib.InvalidArgumentError(_lib.MHTE_INVALID_ARGUMENT,
+                                      "finalize_shared_tensor: the handles are not the same shared tensor")
+  if dtype is not None and first.dtype != dtype:
+    raise TypeError("finalize_shared_tensor: the shared tensor is %s, not %s" % (first.dtype, dtype))
+  if shape is not None:
+    first = first.reshape([-1 if d is None else int(d) for d in shape])
+  return first
