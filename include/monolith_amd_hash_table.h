@@ -575,6 +575,56 @@ mhte_status mhte_split_rows_grad(const void* const* grads, const int64_t* sizes,
                                  void* stream);
 mhte_status mhte_split_launch_counts(int64_t* out, int32_t n);
 
+/* ---- the fused-layout packer (csrc/mhte_sharding_plan.h, mhte_sharding_kernels.h, mhte_sharding_host.h) --
+ * ShardingSparseFids at op version 2 (NT/data/kernels/parse_sparse_feature.cc:106-155 the index arithmetic,
+ * :187-240 FillFidList, :259-424 CreateOffsetTensor; parse_sparse_feature.h:620-990 FeatureParallelParse) for ids
+ * that are parsed and on the device: from every feature's ragged ids to the inputs of mhte_embedding_to_layout and
+ * the fid lists of the parameter servers, one launch sequence for all features.
+ *   features [HOST, n_features] in sorted-name order.  values [dev i64, n_ids], row_splits [dev i64, n_rows + 1];
+ *     n_rows is the batch size, 1 for a shared feature (shared != 0), 0 for a feature the batch does not carry;
+ *     table_index / feature_in_table_index: the feature's table in sorted-name order and its place among that
+ *     table's features (:124-131).  Every (table_index, feature_in_table_index) below table_feature_count occurs once.
+ *   table_feature_count [HOST i32, n_tables], every entry >= 1; ps_num in [1, 1024].
+ *   With F = n_features, N = the ids of all features, R = their rows, n_pre = F * ps_num (the pre-output indices,
+ *   :139-149), n_lists = n_tables * ps_num:
+ *   fid_offset [dev u64, N]  in input order: (pre_output_index + shard * table_feature_count +
+ *     feature_in_table_index) << 32 | rank with shard = uint64(id) % ps_num (:203, :219 — unsigned).  unique == 0:
+ *     rank counts the earlier occurrences of the (feature, shard) (:206); else it is the index of the id's first
+ *     occurrence among the distinct ids of the (feature, shard) (:223) — per feature, never across a table.
+ *   feature_offset [dev i32, R + 1]  one start per (feature, row), then N (:313-320).
+ *   nfl_offset [dev u32, F + 1]  the feature's first row, bit 31 for a shared feature (:307-310); the last entry is
+ *     R + 1, the number of entries of feature_offset (:321).  mhte_embedding_to_layout reads it only to see
+ *     whether a feature has rows (next - own > 0), as RT/ops/fused_embedding_to_layout.cc does.
+ *   fid_list [dev i64, N]  the ids sorted PS-major: shard after shard, inside a shard table after table, inside a
+ *     table feature after feature, inside a feature in (first-)occurrence order — for one shard the values of
+ *     the ragged tensor its raw lookup takes.  The placed ids (N, or the distinct ones) are key_start[n_pre].
+ *   key_start [dev i64, n_pre + 2]  entry shard * F + ft (ft: features numbered table after table) is where that
+ *     (feature, shard) starts in fid_list; entry n_pre the placed ids; entry n_pre + 1 the status word (bit 0: a
+ *     row_splits that does not run from 0 to n_ids without stepping back).
+ *   row_splits_flat [dev i64, n_pre + n_lists]  the reference's fid_list_row_splits, list table_index * ps_num +
+ *     shard after list (parse_sparse_feature.h:853-898), table_feature_count + 1 entries each.
+ *   list_bounds [dev i64, n_lists * 2]  start and size of list table_index * ps_num + shard inside fid_list.
+ *   host_out [HOST i64, n_pre + 2] or NULL: key_start, copied after synchronising the stream — every size in one
+ *     read; a set status bit is then "The input ragged tensor is invalid.".  With NULL the call waits for nothing.
+ * Ranks come from the stable group sort (ballots) and lower bounds; the unique form finds first occurrences with
+ * atomicMin over positions, whose result does not depend on arrival order: the same input gives the same bits on
+ * every run.  InvalidArgument, checked on the host before any device call: ps_num outside [1, 1024], a null or
+ * misaligned (8 bytes; feature_offset / nfl_offset 4) pointer, an index outside its table, a feature with more
+ * than 2^32 - 1 ids (the rank is 32 bits), N of 2^31 - 1 or more. */
+typedef struct {
+  const int64_t* values;
+  const int64_t* row_splits;
+  int64_t n_ids;
+  int32_t n_rows, shared;
+  int32_t table_index, feature_in_table_index;
+} mhte_shard_feature;
+mhte_status mhte_sharding_sparse_fids(const mhte_shard_feature* features, int32_t n_features,
+                                      const int32_t* table_feature_count, int32_t n_tables, int32_t ps_num,
+                                      int32_t unique, uint64_t* fid_offset, int32_t* feature_offset,
+                                      uint32_t* nfl_offset, int64_t* fid_list, int64_t* key_start,
+                                      int64_t* row_splits_flat, int64_t* list_bounds, int64_t* host_out,
+                                      void* stream);
+
 /* MonolithFusedReduceAndSplitGPU / MonolithFusedReduceAndSplitGPUGrad (RT/ops/reduce_op.cu.cc:290-379,
  * :392-475 forward; :477-534, :536-... gradient; NT/distribution_ops.py:838-884), the pooling of the
  * feature-column path (NT/feature.py:519-541), and on the same entry points the CPU op

@@ -11,4 +11,12 @@ raises.
 from monolith_amd import entry  # noqa: F401
 from monolith_amd._lib import build_library, library_path, MhteError  # noqa: F401
 
-__all__ = ["entry", "build_library", "library_path", "MhteError"]
+__all__ = ["entry", "build_library", "library_path", "MhteError", "PartitionedHashTable"]
+
+
+def __getattr__(name):
+  # (the class needs torch and the library; the package itself imports without either)
+  if name == "PartitionedHashTable":
+    from monolith_amd.partitioned_hash_table import PartitionedHashTable
+    return PartitionedHashTable
+  raise AttributeError("module 'monolith_amd' has no attribute %r" % name)

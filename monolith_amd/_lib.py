@@ -78,6 +78,12 @@ class LayoutSlice(C.Structure):
               ("out_index", C.c_int32), ("out_offset", C.c_int32), ("out_row_floats", C.c_int32)]
 
 
+class ShardFeature(C.Structure):
+  _fields_ = [("values", C.c_void_p), ("row_splits", C.c_void_p), ("n_ids", C.c_int64),
+              ("n_rows", C.c_int32), ("shared", C.c_int32), ("table_index", C.c_int32),
+              ("feature_in_table_index", C.c_int32)]
+
+
 class TableStats(C.Structure):
   _fields_ = [("size", C.c_int64), ("hashpower", C.c_int32), ("rows_allocated", C.c_int64),
               ("lookup_hits", C.c_int64), ("dropped", C.c_int64), ("evicted", C.c_int64),
@@ -96,7 +102,7 @@ _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
             "mhte_status": C.c_int32}
 # the structs Python mirrors: a pointer to another struct is a type error at the call
 _MIRRORS = {"mhte_table_config": TableConfig, "mhte_layout_slice": LayoutSlice,
-            "mhte_table_stats": TableStats}
+            "mhte_table_stats": TableStats, "mhte_shard_feature": ShardFeature}
 _TYPE_RE = re.compile(r"(const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)?\s*(\[\d*\])?")
 
 

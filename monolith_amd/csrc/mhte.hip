@@ -44,6 +44,7 @@
 #include "mhte_ffm_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
+#include "mhte_sharding_kernels.h"
 #include "mhte_layout_kernels.h"
 #include "mhte_step_kernels.h"
 #include "mhte_mstep_kernels.h"
@@ -2024,6 +2025,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_dense_opt_host.h"
 #include "mhte_ffm_host.h"
 #include "mhte_split_host.h"
+#include "mhte_sharding_host.h"
 
 struct mhte_multi_step {
   mhte::MultiStep ms;
@@ -2817,6 +2819,20 @@ mhte_status mhte_split_launch_counts(int64_t* out, int32_t n) {
     if (n != kSplitCounters)
       arg_bad("split_launch_counts", "n must be " + std::to_string(kSplitCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kSplitCounters; ++i) out[i] = g_split_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- the fused-layout packer (csrc/mhte_sharding_plan.h, mhte_sharding_kernels.h, mhte_sharding_host.h) --
+mhte_status mhte_sharding_sparse_fids(const mhte_shard_feature* features, int32_t n_features,
+                                      const int32_t* table_feature_count, int32_t n_tables, int32_t ps_num,
+                                      int32_t unique, uint64_t* fid_offset, int32_t* feature_offset,
+                                      uint32_t* nfl_offset, int64_t* fid_list, int64_t* key_start,
+                                      int64_t* row_splits_flat, int64_t* list_bounds, int64_t* host_out,
+                                      void* stream) {
+  return guard([&] {
+    sharding_sparse_fids(features, n_features, table_feature_count, n_tables, ps_num, unique, fid_offset,
+                         feature_offset, nfl_offset, fid_list, key_start, row_splits_flat, list_bounds, host_out,
+                         stream);
   });
 }
 

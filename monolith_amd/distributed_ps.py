@@ -11,7 +11,8 @@ A call is the reference's sequence, op for op:
   fill_with_offset_map / fill_with_offset_map_gradient -> finalize_shared_tensor -> get_embeddings
 
 Out of scope: the transfer_float16 / non-raw branch, map_id_to_embedding, assign / assign_add /
-reinitialize through the shards.
+reinitialize through the shards.  The fused-layout branch (``enable_fused_layout``: ShardingSparseFids ->
+PartitionedHashTable -> fused_embedding_to_layout) is ``partitioned_hash_table.PartitionedHashTable`` (§4.16).
 """
 from typing import Dict, List, Optional, Tuple
 

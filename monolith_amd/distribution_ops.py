@@ -587,6 +587,208 @@ def fused_embedding_to_layout_grad(embeddings_list: List[torch.Tensor], fid_offs
   return grads
 
 
+# ---- the fused-layout packer: from per-feature ragged ids to the layout op's inputs and the PS fid lists ---------
+# (reference ShardingSparseFids at op version 2: data/kernels/parse_sparse_feature.cc:106-155, :187-240, :259-424,
+# parse_sparse_feature.h:620-990)
+SHARDING_TILE = 4096   # ids a workgroup of the packer's stable sort ranks at a time (kGsWaves * kGsRound)
+_UINT32 = getattr(torch, "uint32", None)
+_UINT64 = getattr(torch, "uint64", None)
+
+
+class ShardingIndex(NamedTuple):
+  """The index arithmetic of a configuration (parse_sparse_feature.cc:106-155): features and tables in sorted-name
+  order; per feature its table, its place among the table's features and its place in table-major order."""
+  feature_names: List[str]
+  table_names: List[str]
+  table_index: List[int]
+  feature_in_table_index: List[int]
+  table_feature_count: List[int]
+  table_first: List[int]            # [n_tables + 1]: the table's first feature in table-major order
+  pre_output_index: List[int]       # per feature, for a given ps_num: table_first * ps_num
+
+  @staticmethod
+  def of(feature_cfgs: "FeatureConfigs", ps_num: int) -> "ShardingIndex":
+    names = sorted(feature_cfgs.feature_configs)
+    tables = sorted({feature_cfgs.feature_configs[n].table for n in names})
+    t_of = {t: i for i, t in enumerate(tables)}
+    count = [0] * len(tables)
+    t_idx, fit = [], []
+    for n in names:
+      t = t_of[feature_cfgs.feature_configs[n].table]
+      t_idx.append(t)
+      fit.append(count[t])
+      count[t] += 1
+    first = [0]
+    for c in count:
+      first.append(first[-1] + c)
+    return ShardingIndex(names, tables, t_idx, fit, count, first, [first[t] * ps_num for t in t_idx])
+
+
+class ShardedFids(NamedTuple):
+  fid_offset: torch.Tensor              # uint64 [N], input order
+  feature_offset: torch.Tensor          # int32 [R + 1]
+  nfl_offset: torch.Tensor              # uint32 [F + 1]
+  batch_size: int
+  fid_list: Optional[List[torch.Tensor]]          # [table_index * ps_num + shard]: views of fid_list_flat
+  fid_list_row_splits: Optional[List[np.ndarray]]  # the same index: table_feature_count + 1 entries each, host
+  fid_list_flat: torch.Tensor           # int64 [N]: the placed ids, PS after PS (see ``ps_ragged``)
+  key_start: torch.Tensor               # int64 [F * ps_num + 2] on the device (mhte_sharding_sparse_fids)
+  row_splits_flat: torch.Tensor         # int64 [F * ps_num + n_tables * ps_num] on the device: every list's row_splits
+  list_bounds: torch.Tensor             # int64 [n_tables * ps_num, 2] on the device: start, size in fid_list_flat
+  key_start_host: Optional[np.ndarray]  # None in the plan variant
+  index: ShardingIndex
+  ps_num: int
+
+  def ps_ragged(self, shard: int) -> Ragged:
+    """What PS ``shard`` looks up: its ids of every table, tables in sorted-name order (values: a view)."""
+    ks, F = self.key_start_host, len(self.index.feature_names)
+    lo = shard * F
+    splits = np.ascontiguousarray([ks[lo + f] - ks[lo] for f in self.index.table_first], dtype=np.int64)
+    return Ragged(self.fid_list_flat[int(ks[lo]):int(ks[lo + F])], splits)
+
+  def pre_output_sizes(self) -> np.ndarray:
+    """ids per pre-output index (the rows of the layout op's embeddings_list entries)."""
+    ks, F, ix = self.key_start_host, len(self.index.feature_names), self.index
+    out = np.zeros(F * self.ps_num, dtype=np.int64)
+    for t, tfc in enumerate(ix.table_feature_count):
+      for s in range(self.ps_num):
+        lo, k0 = s * F + ix.table_first[t], ix.table_first[t] * self.ps_num + s * tfc
+        out[k0:k0 + tfc] = np.diff(ks[lo:lo + tfc + 1])
+    return out
+
+
+def _sharding_feature(name, x, shared, dev):
+  """-> (values, row_splits or None when implied, host row_splits?)"""
+  what = "sharding_sparse_fids: feature %s" % name
+  if isinstance(x, torch.Tensor):
+    values, rs = x, None
+    if not shared:
+      raise TypeError("%s: only a shared feature is a single list; give (values, row_splits)" % what)
+  else:
+    values, rs = x[0], x[1]
+  if not isinstance(values, torch.Tensor) or values.dtype != torch.int64:
+    raise TypeError("%s: ids must be an int64 torch tensor, got %s" %
+                    (what, values.dtype if isinstance(values, torch.Tensor) else type(values).__name__))
+  if not values.is_cuda:
+    raise TypeError("%s: ids must be on the GPU (there is no CPU path)" % what)
+  if values.dim() != 1 or not values.is_contiguous():
+    raise ValueError("%s: ids must be a contiguous 1-d tensor" % what)
+  if dev is not None and values.device != dev:
+    raise ValueError("%s: ids are on %s, other features on %s" % (what, values.device, dev))
+  n = values.numel()
+  if rs is None:
+    rs = np.array([0, n], dtype=np.int64)
+  if isinstance(rs, torch.Tensor):
+    if rs.dtype != torch.int64 or not rs.is_cuda or rs.dim() != 1 or not rs.is_contiguous() or rs.numel() < 1:
+      raise TypeError("%s: row_splits on the device must be a contiguous 1-d int64 tensor" % what)
+  else:
+    rs = _checked_row_splits(rs, n)
+  n_rows = (rs.numel() if isinstance(rs, torch.Tensor) else rs.size) - 1
+  if shared and n_rows != 1:
+    raise ValueError("%s: a shared feature has one row, got %d" % (what, n_rows))
+  return values, rs, n_rows
+
+
+def _sharding_sparse_fids(features, feature_cfgs, ps_num, unique, shared_features, batch_size, want_host):
+  what = "sharding_sparse_fids"
+  if not isinstance(ps_num, int) or isinstance(ps_num, bool):
+    raise TypeError("%s: ps_num must be an int, got %r" % (what, ps_num))
+  ix = ShardingIndex.of(feature_cfgs, max(ps_num, 1))
+  shared_features = set(shared_features)
+  unknown = sorted((set(features) | shared_features) - set(ix.feature_names))
+  if unknown:
+    raise _lib.InvalidArgumentError(_lib.MHTE_INVALID_ARGUMENT,
+                                    "%s: no feature config for %s" % (what, ", ".join(unknown)))
+  if not features:
+    raise ValueError("%s: no features" % what)
+  dev, parsed, host_rs, batch = None, {}, [], batch_size
+  for name in ix.feature_names:
+    if name not in features:
+      continue
+    shared = name in shared_features
+    values, rs, n_rows = _sharding_feature(name, features[name], shared, dev)
+    dev = values.device
+    if not shared:
+      if batch is not None and n_rows != batch:
+        raise ValueError("%s: feature %s has %d rows, the batch %d" % (what, name, n_rows, batch))
+      batch = n_rows
+    if not isinstance(rs, torch.Tensor):
+      host_rs.append(rs)
+    parsed[name] = (values, rs, n_rows)
+  if batch is None:
+    raise ValueError("%s: batch_size is needed when every feature is shared" % what)
+  # the host row_splits of the call travel in one upload
+  rs_dev = torch.from_numpy(np.concatenate(host_rs)).to(dev) if host_rs else None
+  F, T = len(ix.feature_names), len(ix.table_names)
+  feats = (_lib.ShardFeature * F)()
+  n_total = rows = at = 0
+  for f, name in enumerate(ix.feature_names):
+    x = feats[f]
+    x.table_index, x.feature_in_table_index = ix.table_index[f], ix.feature_in_table_index[f]
+    x.shared = int(name in shared_features)
+    if name not in parsed:
+      continue
+    values, rs, n_rows = parsed[name]
+    x.values, x.n_ids, x.n_rows = values.data_ptr(), values.numel(), n_rows
+    if isinstance(rs, torch.Tensor):
+      x.row_splits = rs.data_ptr()
+    else:
+      x.row_splits = rs_dev.data_ptr() + 8 * at
+      at += rs.size
+    n_total += values.numel()
+    rows += n_rows
+  n_pre, n_lists = F * max(ps_num, 0), T * max(ps_num, 0)
+  fid_offset = torch.empty(n_total, dtype=torch.int64, device=dev)
+  feature_offset = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+  nfl_offset = torch.empty(F + 1, dtype=torch.int32, device=dev)
+  fid_list = torch.empty(n_total, dtype=torch.int64, device=dev)
+  key_start = torch.empty(n_pre + 2, dtype=torch.int64, device=dev)
+  rs_flat = torch.empty(n_pre + n_lists, dtype=torch.int64, device=dev)
+  bounds = torch.empty((n_lists, 2), dtype=torch.int64, device=dev)
+  host = np.empty(n_pre + 2, dtype=np.int64) if want_host else None
+  tfc = (C.c_int32 * T)(*ix.table_feature_count)
+  with torch.cuda.device(dev):
+    check(_lib.lib().mhte_sharding_sparse_fids(
+        feats, F, tfc, T, ps_num, int(bool(unique)), vp(fid_offset), vp(feature_offset), vp(nfl_offset), vp(fid_list),
+        vp(key_start), vp(rs_flat), vp(bounds), None if host is None else host.ctypes.data_as(C.c_void_p), _stream()))
+  if _UINT64 is not None and _UINT32 is not None:   # (the bits are the op's; older torch keeps the signed containers)
+    fid_offset, nfl_offset = fid_offset.view(_UINT64), nfl_offset.view(_UINT32)
+  lists = splits = None
+  if host is not None:
+    lists, splits = [], []
+    for t in range(T):
+      for s in range(ps_num):
+        lo = s * F + ix.table_first[t]
+        ks = host[lo:lo + ix.table_feature_count[t] + 1]
+        lists.append(fid_list[int(ks[0]):int(ks[-1])])
+        splits.append(np.ascontiguousarray(ks - ks[0]))
+  return ShardedFids(fid_offset, feature_offset, nfl_offset, int(batch), lists, splits, fid_list, key_start, rs_flat,
+                     bounds, host, ix, ps_num)
+
+
+def sharding_sparse_fids(features, feature_cfgs: FeatureConfigs, ps_num: int, unique: bool = True,
+                         shared_features=(), batch_size: Optional[int] = None) -> ShardedFids:
+  """ShardingSparseFids at op version 2 for parsed ids on the device (mhte_sharding_sparse_fids): dedups
+  (``unique``) and shards every feature's ids and emits what ``fused_embedding_to_layout`` takes — ``fid_offset``,
+  ``feature_offset``, ``nfl_offset`` — beside the fid lists of every (table, shard) with their row_splits
+  (index ``table_index * ps_num + shard``, tables and features in sorted-name order).
+
+  ``features``: {feature name: (values, row_splits)} — int64 ids on the GPU, row_splits of batch + 1 entries on
+  the host (numpy, as ``Ragged`` carries them) or on the device (int64); a feature named in ``shared_features``
+  is a single list: a 1-d tensor, or (values, [0, n]).  A configured feature the batch does not carry has no
+  rows.  ``shard = uint64(id) % ps_num``.  Every size comes back in one host read; ``sharding_sparse_fids_plan``
+  reads nothing back."""
+  return _sharding_sparse_fids(features, feature_cfgs, ps_num, unique, shared_features, batch_size, True)
+
+
+def sharding_sparse_fids_plan(features, feature_cfgs: FeatureConfigs, ps_num: int, unique: bool = True,
+                              shared_features=(), batch_size: Optional[int] = None) -> ShardedFids:
+  """``sharding_sparse_fids`` with everything left on the device, for callers who chain on the stream: no wait,
+  no host copy — ``fid_list`` / ``fid_list_row_splits`` / ``key_start_host`` are None; the lists are described by
+  ``list_bounds`` and ``row_splits_flat``, and ``key_start[-1]`` is the status word (bit 0: invalid row_splits)."""
+  return _sharding_sparse_fids(features, feature_cfgs, ps_num, unique, shared_features, batch_size, False)
+
+
 def lookup_gradient(id_indices: torch.Tensor, id_values: torch.Tensor,
                     input_grads: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
   """MonolithHashTableLookupGradient (runtime/ops/hash_table_lookup_op.cc:110-147): the gradient of a
