@@ -529,6 +529,41 @@ mhte_status mhte_ffm_grad(const float* grad, int64_t grad_cols, const float* lef
                           float* left_grad, float* right_grad, void* stream);
 mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n);
 
+/* ---- in-batch AUC loss (csrc/mhte_auc_core.h, mhte_auc_kernels.h, mhte_auc_host.h) -----------------------
+ * The ops InbatchAucLoss and InbatchAucLossGrad (RT/ops/inbatch_auc_loss.cc:30-138: CPU only, two nested loops,
+ * one float accumulator; Python NT/losses/inbatch_auc_loss.py, test NT/losses/inbatch_auc_loss_test.py): the leg
+ * from the dense tower's logit to the dy of its backward.  label, logit [dev f32, n] (any shape, n elements):
+ *   element i is positive if label[i] > 0, negative if it is not positive and label[i] > -10000, ignored
+ *   otherwise (a NaN label is ignored).  For every positive i and negative j, diff = logit[i] - logit[j]:
+ *     -87 < diff < 88:   t = diff - log(1 + exp(diff)),  s = 1 - 1 / (1 + exp(-diff))
+ *     diff <= -87:       t = diff,                       s = 1
+ *     otherwise (diff >= 88 or NaN):  t = 0,             s = 0
+ *   loss = sum t_ij (<= 0, the reference's sign);  logit_grad[i] = grad * sum_j s_ij for a positive,
+ *   logit_grad[j] = -grad * neg_weight * sum_i s_ij for a negative, +0 for an ignored element, for every element
+ *   when there is no positive or no negative, and wherever the product is a zero of either sign.
+ * The middle branch is fp32 in the form that cancels nothing, e = exp(-|diff|): t = -log1p(e) resp.
+ * diff - log1p(e), s = e / (1 + e) resp. 1 / (1 + e) for diff >= 0 resp. < 0.  Every sum is fp64, in an order
+ * fixed by n and the two counts, rounded to fp32 once (the gradient after the multiplication by neg_weight and
+ * grad); no atomics: the same bits on every run.
+ *   mhte_inbatch_auc_loss:       loss [dev f32, 1]; unit_grad [dev f32, n] or NULL: the gradient for grad = 1,
+ *                                from the same launches (t and s share e).
+ *   mhte_inbatch_auc_loss_grad:  logit_grad [dev f32, n]; grad_dev NULL, or a device word that replaces grad.
+ * Five launches per call (classes per tile, their scan, the stable compaction of both classes, the pair kernel,
+ * the final pass), none for n == 0 (the loss is then cleared to +0 by a memset).  The number of positives and
+ * negatives stays in device words: no entry point waits for the device, reads a device value or allocates beyond
+ * the first growth of the per-device workspace (about 9 MB at n = 65536), so a call can be captured into a graph.
+ * mhte_inbatch_auc_launch_counts: the launches of this process by kernel form, n must be 9, index 0 count,
+ *   1 scan, 2 scatter, 3 / 4 / 5 the pair kernel for the loss alone / loss and gradient / gradient alone,
+ *   6 / 7 / 8 the final pass for the same.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand (loss always), a pointer that is not 4-byte aligned, n < 0 or
+ * n >= 2^31, a neg_weight outside (0, 1] or NaN (the reference CHECKs it in the forward only; both refuse it). */
+mhte_status mhte_inbatch_auc_loss(const float* label, const float* logit, int64_t n, float neg_weight, float* loss,
+                                  float* unit_grad, void* stream);
+mhte_status mhte_inbatch_auc_loss_grad(const float* label, const float* logit, int64_t n, float grad,
+                                       const float* grad_dev, float neg_weight, float* logit_grad, void* stream);
+mhte_status mhte_inbatch_auc_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

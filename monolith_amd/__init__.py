@@ -11,7 +11,9 @@ raises.
 from monolith_amd import entry  # noqa: F401
 from monolith_amd._lib import build_library, library_path, MhteError  # noqa: F401
 
-__all__ = ["entry", "build_library", "library_path", "MhteError", "PartitionedHashTable"]
+_LOSSES = ("inbatch_auc_loss", "inbatch_auc_loss_grad", "inbatch_auc_launch_counts")
+
+__all__ = ["entry", "build_library", "library_path", "MhteError", "PartitionedHashTable", "losses"] + list(_LOSSES)
 
 
 def __getattr__(name):
@@ -19,4 +21,8 @@ def __getattr__(name):
   if name == "PartitionedHashTable":
     from monolith_amd.partitioned_hash_table import PartitionedHashTable
     return PartitionedHashTable
+  if name == "losses" or name in _LOSSES:
+    import importlib
+    losses = importlib.import_module("monolith_amd.losses")
+    return losses if name == "losses" else getattr(losses, name)
   raise AttributeError("module 'monolith_amd' has no attribute %r" % name)

@@ -42,6 +42,7 @@
 #include "mhte_flat_kernels.h"
 #include "mhte_dense_opt_kernels.h"
 #include "mhte_ffm_kernels.h"
+#include "mhte_auc_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -2024,6 +2025,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_flat_host.h"
 #include "mhte_dense_opt_host.h"
 #include "mhte_ffm_host.h"
+#include "mhte_auc_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 
@@ -2787,6 +2789,26 @@ mhte_status mhte_ffm_launch_counts(int64_t* out, int32_t n) {
     if (n != kFfmCounters)
       arg_bad("ffm_launch_counts", "n must be " + std::to_string(kFfmCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kFfmCounters; ++i) out[i] = g_ffm_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- in-batch AUC loss (csrc/mhte_auc_core.h, mhte_auc_kernels.h, mhte_auc_host.h) ---------------------
+mhte_status mhte_inbatch_auc_loss(const float* label, const float* logit, int64_t n, float neg_weight, float* loss,
+                                  float* unit_grad, void* stream) {
+  return guard([&] { auc_forward(label, logit, n, neg_weight, loss, unit_grad, stream); });
+}
+
+mhte_status mhte_inbatch_auc_loss_grad(const float* label, const float* logit, int64_t n, float grad,
+                                       const float* grad_dev, float neg_weight, float* logit_grad, void* stream) {
+  return guard([&] { auc_gradient(label, logit, n, grad, grad_dev, neg_weight, logit_grad, stream); });
+}
+
+mhte_status mhte_inbatch_auc_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "inbatch_auc_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kAucCounters) arg_bad(op, "n must be " + std::to_string(kAucCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kAucCounters; ++i) out[i] = g_auc_launches[i].load(std::memory_order_relaxed);
   });
 }
 
