@@ -564,6 +564,51 @@ mhte_status mhte_inbatch_auc_loss_grad(const float* label, const float* logit, i
                                        const float* grad_dev, float neg_weight, float* logit_grad, void* stream);
 mhte_status mhte_inbatch_auc_launch_counts(int64_t* out, int32_t n);
 
+/* ---- batch softmax loss (csrc/mhte_bsm_core.h, mhte_bsm_kernels.h, mhte_bsm_host.h) ------------------------
+ * The sampling-bias-corrected in-batch softmax of the two-tower model (NT/losses/batch_softmax_loss.py:18-57), the
+ * consumer of the interval that MHTE_OPT_BATCH_SOFTMAX keeps per item id.  query, item [dev f32, batch x dim],
+ * item_step_interval, r [dev f32, batch]:
+ *   q^_i = q_i * rsqrt(max(sum q_i^2, 1e-12)), likewise i^_j (normalize = 1; the rows themselves for 0)
+ *   z_ij = (q^_i . i^_j) / temperature + log(max(item_step_interval_j, 1))
+ *   loss = -sum_i r_i * (z_ii - lse_i),  lse_i = m_i + log sum_j exp(z_ij - m_i),  m_i = max_j z_ij
+ * The one defined deviation: the reference takes exp of the unshifted z and divides, which overflows in fp32
+ * (normalised rows at temperature 0.01: exp(100) = inf, inf / inf = NaN); this is the same value wherever the
+ * reference's own fp32 evaluation is finite and stays finite where it is not.
+ * Gradients for query and item only (BatchSoftmaxOptimizer ignores its gradient; r gets none), with
+ * G_ij = r_i * (exp(z_ij - lse_i) - [i == j]):  g_q^ = G . I^ / temperature, g_i^ = G^T . Q^ / temperature, then
+ * through the normalisation of a row x, s = sum x^2, inv = rsqrt(max(s, 1e-12)):  dx = (g - x^ (x^ . g)) * inv for
+ * s >= 1e-12, g * inv below.  A gradient that is a zero of either sign is written as +0.
+ * The batch x batch matrix is never stored: tiles of it come from the f32-input MFMA (exact fp32, an fmaf chain
+ * in a fixed permuted order), rows keep a running maximum and sum, the backward recomputes the tiles once per gradient.  No
+ * atomics; the split of the columns into chunks is a function of (batch, dim) alone: the same bits on every run,
+ * and whether a gradient is asked for together with the loss or on its own.
+ *   mhte_batch_softmax_loss:       loss [dev f32, 1]; unit_dquery, unit_ditem [dev f32, batch x dim] or NULL: the
+ *                                  gradients for grad = 1.  batch == 0: no launch, the loss is cleared to +0.
+ *   mhte_batch_softmax_loss_grad:  dquery, ditem (at least one non-NULL), scaled by grad, or by the device word
+ *                                  grad_dev when that is not NULL.
+ *   mhte_batch_softmax_plan:       n must be 5: out = row block, column tile, chunks per row block, chunks per
+ *                                  column block, workspace bytes (needs no device).
+ *   mhte_batch_softmax_launch_counts: the launches of this process by kernel form, n must be 6: 0 prep, 1 row
+ *                                  (forward), 2 row (gradient), 3 col, 4 final (lse, loss), 5 final (gradients).
+ * Launches per call: 3 for the loss alone (prep, row, final), 4 + one per gradient with gradients (prep, row,
+ * final, row gradient and / or col, final gradient), in both entry points.  No entry point waits for the device,
+ * reads a device value or allocates beyond the first growth of the per-device workspace
+ * (4 * (7 bp + 2 bp kp + 2 chunks bp (1 + kp)) bytes, bp and kp the padded extents: 66.2 MiB at 65536 x 64), so a
+ * call can be captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand (loss always), a pointer that is not 4-byte aligned, batch < 0 or
+ * >= 2^24, dim outside [1, 256], a temperature that is not > 0 (NaN included), a normalize that is neither 0 nor
+ * 1, a grad entry with both outputs NULL. */
+mhte_status mhte_batch_softmax_loss(const float* query, const float* item, const float* item_step_interval,
+                                    const float* r, int64_t batch, int32_t dim, int32_t normalize, float temperature,
+                                    float* loss, float* unit_dquery, float* unit_ditem, void* stream);
+mhte_status mhte_batch_softmax_loss_grad(const float* query, const float* item, const float* item_step_interval,
+                                         const float* r, int64_t batch, int32_t dim, int32_t normalize,
+                                         float temperature, float grad, const float* grad_dev, float* dquery,
+                                         float* ditem, void* stream);
+mhte_status mhte_batch_softmax_plan(int64_t batch, int32_t dim, int64_t* out, int32_t n);
+mhte_status mhte_batch_softmax_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

@@ -11,7 +11,8 @@ raises.
 from monolith_amd import entry  # noqa: F401
 from monolith_amd._lib import build_library, library_path, MhteError  # noqa: F401
 
-_LOSSES = ("inbatch_auc_loss", "inbatch_auc_loss_grad", "inbatch_auc_launch_counts")
+_LOSSES = ("inbatch_auc_loss", "inbatch_auc_loss_grad", "inbatch_auc_launch_counts", "batch_softmax_loss",
+           "batch_softmax_loss_grad", "batch_softmax_plan", "batch_softmax_launch_counts")
 
 __all__ = ["entry", "build_library", "library_path", "MhteError", "PartitionedHashTable", "losses"] + list(_LOSSES)
 

@@ -43,6 +43,7 @@
 #include "mhte_dense_opt_kernels.h"
 #include "mhte_ffm_kernels.h"
 #include "mhte_auc_kernels.h"
+#include "mhte_bsm_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -2026,6 +2027,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_dense_opt_host.h"
 #include "mhte_ffm_host.h"
 #include "mhte_auc_host.h"
+#include "mhte_bsm_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 
@@ -2809,6 +2811,39 @@ mhte_status mhte_inbatch_auc_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kAucCounters) arg_bad(op, "n must be " + std::to_string(kAucCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kAucCounters; ++i) out[i] = g_auc_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- batch softmax loss (csrc/mhte_bsm_core.h, mhte_bsm_kernels.h, mhte_bsm_host.h) ----------------------
+mhte_status mhte_batch_softmax_loss(const float* query, const float* item, const float* item_step_interval,
+                                    const float* r, int64_t batch, int32_t dim, int32_t normalize, float temperature,
+                                    float* loss, float* unit_dquery, float* unit_ditem, void* stream) {
+  return guard([&] {
+    bsm_forward(query, item, item_step_interval, r, batch, dim, normalize, temperature, loss, unit_dquery, unit_ditem,
+                stream);
+  });
+}
+
+mhte_status mhte_batch_softmax_loss_grad(const float* query, const float* item, const float* item_step_interval,
+                                         const float* r, int64_t batch, int32_t dim, int32_t normalize,
+                                         float temperature, float grad, const float* grad_dev, float* dquery,
+                                         float* ditem, void* stream) {
+  return guard([&] {
+    bsm_gradient(query, item, item_step_interval, r, batch, dim, normalize, temperature, grad, grad_dev, dquery, ditem,
+                 stream);
+  });
+}
+
+mhte_status mhte_batch_softmax_plan(int64_t batch, int32_t dim, int64_t* out, int32_t n) {
+  return guard([&] { bsm_plan_out(batch, dim, out, n); });
+}
+
+mhte_status mhte_batch_softmax_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "batch_softmax_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kBsmCounters) arg_bad(op, "n must be " + std::to_string(kBsmCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kBsmCounters; ++i) out[i] = g_bsm_launches[i].load(std::memory_order_relaxed);
   });
 }
 
