@@ -609,6 +609,57 @@ mhte_status mhte_batch_softmax_loss_grad(const float* query, const float* item, 
 mhte_status mhte_batch_softmax_plan(int64_t batch, int32_t dim, int64_t* out, int32_t n);
 mhte_status mhte_batch_softmax_launch_counts(int64_t* out, int32_t n);
 
+/* ---- FeatureInsight (csrc/mhte_fi_core.h, mhte_fi_kernels.h, mhte_fi_host.h) -------------------------------
+ * The ops FeatureInsight and FeatureInsightGrad (NT/layers/ops/feature_insight_ops.cc,
+ * NT/layers/kernels/feature_insight_kernels.cc:70-83 and :148-160, NT/layers/layer_ops.py:49-85): the
+ * block-diagonal product of the concatenated embeddings with the first dense layer's kernel, one block per feature.
+ * input [dev f32, batch x in_cols], weight [dev f32, in_cols x k], segment_sizes [HOST i32, n_segments], their sum
+ * in_cols; segment f covers the columns o_f .. o_f + s_f - 1 of input and the same rows of weight:
+ *   out[b, f k + c]    = sum_{j in seg f} input[b, j] * weight[j, c]          [batch x n_segments k]
+ *   input_grad[b, j]   = sum_c grad[b, f(j) k + c] * weight[j, c]             [batch x in_cols]
+ *   weight_grad[j, c]  = sum_b grad[b, f(j) k + c] * input[b, j]              [in_cols x k]
+ *   agg[b, f]          = sum_c out[b, f k + c]^2                              [batch x n_segments]
+ * Products are exact fp32: every sum is an fmaf chain from +0 in ascending order (over the segment, over c, over
+ * the rows of a batch slab); the slabs of weight_grad are added in slab order; agg squares the very bits the plain
+ * op stores, in 16 interleaved chains added in order (csrc/mhte_fi_core.h states the definition).  No atomics; the
+ * order of every sum is a function of the shape alone: the same bits on every run, from either entry point, and
+ * whichever gradients are asked for.  A segment of size 0 is legal: its k output columns, and its agg entry, are
+ * +0.  Every zero written is +0.
+ *   mhte_feature_insight:       aggregate 0: out [dev f32, batch x out_cols], out_cols == n_segments * k;
+ *                               aggregate 1: the fused form, out is agg, out_cols == n_segments: no intermediate
+ *                               and no workspace.  batch == 0: no launch.
+ *   mhte_feature_insight_grad:  grad [dev f32, batch x grad_cols], grad_cols == n_segments * k; input_grad,
+ *                               weight_grad: either may be NULL, not both.  batch == 0: weight_grad is cleared to
+ *                               +0 (one memset), nothing else.
+ *   mhte_feature_insight_plan:  n must be 9: out = row block, column tile, chain terms per LDS stage, segments per
+ *                               launch, launches per kernel form (groups), rows per batch slab, batch slabs of the
+ *                               weight gradient, workspace bytes of the forward (0 in both modes), workspace bytes
+ *                               of the gradient (slabs * in_cols * k * 4 for more than one slab, else 0).  Needs no
+ *                               device, a function of (batch, in_cols, k, n_segments) alone.
+ *   mhte_feature_insight_launch_counts: the launches of this process by kernel form, n must be 5: 0 forward,
+ *                               1 aggregate, 2 input gradient, 3 weight gradient, 4 slab sum.
+ * The segment offsets of a launch ride in its kernel arguments, 128 segments per launch; a longer list is cut into
+ * groups of 128 consecutive segments, one launch per group and kernel form: nothing is uploaded, so nothing can be
+ * stale under graph replay or when the list changes between calls.  n_segments is at most 4096 (32 launches).
+ * Launches per call: groups (forward, either mode); groups per gradient asked for, groups that hold only empty
+ * segments left out, plus the slab sum when the plan has more than one slab.  No entry point waits for the device,
+ * reads a device value or allocates beyond the first growth of the per-device workspace (the slab partials), so a
+ * call can be captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand (segment_sizes always), a pointer that is not 4-byte aligned,
+ * batch < 0 or > 2^30 - 64, in_cols outside [0, 4194240], k outside [1, 4194240], n_segments outside [1, 4096], a
+ * negative segment size, a sum of sizes that is not in_cols, batch * n_segments * k beyond 2^60, a grad_cols or
+ * out_cols that does not match, an aggregate that is neither 0 nor 1, a grad entry with both outputs NULL. */
+mhte_status mhte_feature_insight(const float* input, const float* weight, int64_t batch, int64_t in_cols, int32_t k,
+                                 const int32_t* segment_sizes, int32_t n_segments, int32_t aggregate, float* out,
+                                 int64_t out_cols, void* stream);
+mhte_status mhte_feature_insight_grad(const float* grad, int64_t grad_cols, const float* input, const float* weight,
+                                      int64_t batch, int64_t in_cols, int32_t k, const int32_t* segment_sizes,
+                                      int32_t n_segments, float* input_grad, float* weight_grad, void* stream);
+mhte_status mhte_feature_insight_plan(int64_t batch, int64_t in_cols, int32_t k, int32_t n_segments, int64_t* out,
+                                      int32_t n);
+mhte_status mhte_feature_insight_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

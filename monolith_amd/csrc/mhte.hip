@@ -44,6 +44,7 @@
 #include "mhte_ffm_kernels.h"
 #include "mhte_auc_kernels.h"
 #include "mhte_bsm_kernels.h"
+#include "mhte_fi_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -2028,6 +2029,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_ffm_host.h"
 #include "mhte_auc_host.h"
 #include "mhte_bsm_host.h"
+#include "mhte_fi_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 
@@ -2844,6 +2846,38 @@ mhte_status mhte_batch_softmax_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kBsmCounters) arg_bad(op, "n must be " + std::to_string(kBsmCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kBsmCounters; ++i) out[i] = g_bsm_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- FeatureInsight (csrc/mhte_fi_core.h, mhte_fi_kernels.h, mhte_fi_host.h) -----------------------------
+mhte_status mhte_feature_insight(const float* input, const float* weight, int64_t batch, int64_t in_cols, int32_t k,
+                                 const int32_t* segment_sizes, int32_t n_segments, int32_t aggregate, float* out,
+                                 int64_t out_cols, void* stream) {
+  return guard([&] {
+    fi_forward(input, weight, batch, in_cols, k, segment_sizes, n_segments, aggregate, out, out_cols, stream);
+  });
+}
+
+mhte_status mhte_feature_insight_grad(const float* grad, int64_t grad_cols, const float* input, const float* weight,
+                                      int64_t batch, int64_t in_cols, int32_t k, const int32_t* segment_sizes,
+                                      int32_t n_segments, float* input_grad, float* weight_grad, void* stream) {
+  return guard([&] {
+    fi_gradient(grad, grad_cols, input, weight, batch, in_cols, k, segment_sizes, n_segments, input_grad, weight_grad,
+                stream);
+  });
+}
+
+mhte_status mhte_feature_insight_plan(int64_t batch, int64_t in_cols, int32_t k, int32_t n_segments, int64_t* out,
+                                      int32_t n) {
+  return guard([&] { fi_plan_out(batch, in_cols, k, n_segments, out, n); });
+}
+
+mhte_status mhte_feature_insight_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "feature_insight_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kFiCounters) arg_bad(op, "n must be " + std::to_string(kFiCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kFiCounters; ++i) out[i] = g_fi_launches[i].load(std::memory_order_relaxed);
   });
 }
 

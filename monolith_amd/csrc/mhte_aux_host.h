@@ -2,7 +2,7 @@
 // scratch (AuxWs), the pinned staging ring for small uploads (PinnedStage), the argument checks they share, and
 // the upload and dispatch of a chunk table (mhte_chunk_table.h).  Included by mhte.hip behind DedupWs and the
 // group kernels, in front of the hosts that need it (mhte_clip_host.h, mhte_flat_host.h, mhte_dense_opt_host.h,
-// mhte_ffm_host.h, mhte_auc_host.h, mhte_bsm_host.h).
+// mhte_ffm_host.h, mhte_auc_host.h, mhte_bsm_host.h, mhte_fi_host.h).
 #ifndef MHTE_AUX_HOST_H_
 #define MHTE_AUX_HOST_H_
 
@@ -24,6 +24,7 @@ struct AuxWs {
   DevBuf<char> split_table;           // ... and the pointer table of its gradient
   DevBuf<char> auc;                   // in-batch AUC loss (mhte_auc_host.h): the plan's arrays, by its offsets
   DevBuf<char> bsm;                   // batch softmax loss (mhte_bsm_host.h): the same
+  DevBuf<char> fi;                    // FeatureInsight (mhte_fi_host.h): the slab partials of the weight gradient
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;
