@@ -33,7 +33,7 @@
 #include <dirent.h>
 #include <ctype.h>
 
-#include "mhte_ckpt.h"
+#include "mhte_ckpt_parts.h"
 #include "mhte_proto_config.h"
 #include <map>
 #include "mhte_pool_kernels.h"
@@ -58,10 +58,6 @@
 namespace mhte {
 
 // ------------------------------------------------------------------------------------------ errors
-struct Error : std::runtime_error {
-  mhte_status code;
-  Error(mhte_status c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 static thread_local std::string g_last_error;
 
 #define HIP_OK(expr)                                                                          \
@@ -110,59 +106,6 @@ struct HostBuf {
     cap = want;
   }
 };
-
-// fn(lo, hi, k) over [0, n) cut into `parts` contiguous ranges, on that many host threads (the
-// caller's included); the first exception is rethrown
-template <typename F>
-static void parallel_ranges(size_t n, int parts, F&& fn) {
-  parts = int(std::max<size_t>(1, std::min<size_t>(size_t(parts), n)));
-  std::vector<std::exception_ptr> err;
-  err.resize(size_t(parts));
-  auto run = [&](int k) {
-    try {
-      fn(n * size_t(k) / size_t(parts), n * size_t(k + 1) / size_t(parts), k);
-    } catch (...) {
-      err[size_t(k)] = std::current_exception();
-    }
-  };
-  std::vector<std::thread> th;
-  for (int k = 1; k < parts; ++k) th.emplace_back(run, k);
-  run(0);
-  for (auto& x : th) x.join();
-  for (auto& e : err)
-    if (e) std::rethrow_exception(e);
-}
-
-// staging of one checkpoint shard job (device scan output, pinned host copies, codec buffers): kept
-// by the table between saves / restores — pinning and unpinning a gigabyte per call costs more than
-// the copy it speeds up
-struct CkptStage {
-  DevBuf<uint32_t> bc;
-  DevBuf<uint64_t> bo;
-  DevBuf<int64_t> d_ids, d_pos;
-  DevBuf<uint32_t> d_ts;
-  DevBuf<float> d_rows;
-  // two sets of everything a save chunk passes from stage to stage (scan -> encode -> write run
-  // beside each other, ckpt::run_pipeline3); restore decodes into set 0
-  HostBuf<int64_t> h_ids[2];
-  HostBuf<uint32_t> h_ts[2];
-  HostBuf<float> h_rows[2];
-  uint64_t h_n[2] = {0, 0};                 // rows of the chunk in the set
-  std::vector<std::string> parts[2];        // framed records of the chunk, one string per codec thread
-  std::vector<uint64_t> part_n[2];
-  ckpt::ByteArena arena[2];   // restore: the stretch being decoded and the one being read ahead
-};
-
-// host threads per checkpoint shard for the EntryDump codec (MHTE_CKPT_THREADS; shards run beside
-// each other on up to 16 threads of their own)
-static int ckpt_codec_threads() {
-  static const int n = [] {
-    if (const char* e = getenv("MHTE_CKPT_THREADS")) return std::max(1, atoi(e));
-    const unsigned hw = std::thread::hardware_concurrency();
-    return int(std::max(1u, std::min(16u, hw / 8u)));
-  }();
-  return n;
-}
 
 static inline uint32_t ceil_log2(uint64_t n) {
   uint32_t l = 0;
@@ -1850,20 +1793,7 @@ inline void DedupWs::adopt_probe(const Table& tb, bool reserved) {
 struct mhte_multi_table {
   int device = 0;
   std::string shared_name;
-  // checkpoint staging, one per concurrent shard job, reused across calls
-  std::mutex stage_mu;
-  std::vector<std::unique_ptr<mhte::CkptStage>> stages;
-  std::unique_ptr<mhte::CkptStage> take_stage() {
-    std::lock_guard<std::mutex> g(stage_mu);
-    if (stages.empty()) return std::unique_ptr<mhte::CkptStage>(new mhte::CkptStage);
-    std::unique_ptr<mhte::CkptStage> s = std::move(stages.back());
-    stages.pop_back();
-    return s;
-  }
-  void give_stage(std::unique_ptr<mhte::CkptStage> s) {
-    std::lock_guard<std::mutex> g(stage_mu);
-    stages.push_back(std::move(s));
-  }
+  mhte::CkptPool ckpt_stages;   // checkpoint staging, one per concurrent shard job, reused across calls
   std::vector<std::unique_ptr<mhte::Table>> tables;  // sorted by name
   // device copies of the tables' views, read by the multi-table launches (mhte_mstep_host.h)
   mhte::DevBuf<mhte::TableView> d_views;
@@ -2032,6 +1962,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_fi_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
+#include "mhte_ckpt_host.h"
 
 struct mhte_multi_step {
   mhte::MultiStep ms;
@@ -2447,38 +2378,7 @@ mhte_status mhte_table_get_stats(mhte_multi_table* t, int32_t table, mhte_table_
 mhte_status mhte_table_dump(mhte_multi_table* t, int32_t table, int64_t cap, int64_t* ids,
                             int64_t* positions, uint32_t* ts, float* rows, int64_t* n_out,
                             void* stream) {
-  return guard([&] {
-    Table& tb = table_at(t, table);
-    HIP_OK(hipSetDevice(t->device));
-    std::lock_guard<std::mutex> g(tb.mu);
-    hipStream_t st = S(stream);
-    tb.finish_pending(st);
-    const uint64_t nslots = (uint64_t(1) << tb.hp) * kSlots;
-    const uint32_t nblocks = uint32_t((nslots + 1023) / 1024);
-    DevBuf<uint32_t> bc;
-    DevBuf<uint64_t> bo;
-    bc.reserve(nblocks);
-    bo.reserve(nblocks);
-    dump_count_kernel<<<nblocks, 256, 0, st>>>(tb.view, uint64_t(0), nslots, bc.p);
-    HIP_OK(hipGetLastError());
-    std::vector<uint32_t> hc(nblocks);
-    HIP_OK(hipMemcpyAsync(hc.data(), bc.p, sizeof(uint32_t) * nblocks, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    std::vector<uint64_t> ho(nblocks);
-    uint64_t acc = 0;
-    for (uint32_t i = 0; i < nblocks; ++i) {
-      ho[i] = acc;
-      acc += hc[i];
-    }
-    *n_out = int64_t(acc);
-    if (int64_t(acc) > cap)
-      throw Error(MHTE_INVALID_ARGUMENT, "dump buffers too small: need " + std::to_string(acc));
-    if (acc == 0) return;
-    HIP_OK(hipMemcpyAsync(bo.p, ho.data(), sizeof(uint64_t) * nblocks, hipMemcpyHostToDevice, st));
-    dump_emit_kernel<<<nblocks, 256, 0, st>>>(tb.view, uint64_t(0), nslots, bo.p, ids, positions, ts, rows);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(st));
-  });
+  return guard([&] { dump_table(t, table_at(t, table), cap, ids, positions, ts, rows, n_out, S(stream)); });
 }
 
 // ---- post-exchange gather + pooling -------------------------------------------------------------
@@ -3580,734 +3480,41 @@ mhte_status mhte_hash_filter_restore(mhte_hash_filter* f, const char* basename, 
   });
 }
 
-// ---- checkpoints in the reference's on-disk format --------------------------------------------
-extern "C++" {
-namespace mhte {
-
-static std::vector<ckpt::SegLayout> seg_layout(const Table& tb) {
-  std::vector<ckpt::SegLayout> v;
-  for (uint32_t i = 0; i < tb.nseg; ++i) {
-    const SegDesc& d = tb.view.seg[i];
-    ckpt::SegLayout s;
-    s.dim = d.dim;
-    s.kind = d.opt;  // (SegKind values are the engine's OptType)
-    s.w_off = d.w_off;
-    s.st_off = d.st_off;
-    v.push_back(s);
-  }
-  return v;
-}
-
-static int64_t ttl_days_of(const Table& tb, int64_t id) {
-  const int64_t slot = (id >> 48) & 0x7fff;  // slot_id_v2, reader_util.h:36-38
-  int64_t days = tb.default_expire_days;
-  for (size_t i = 0; i < tb.expire_slots.size(); ++i)
-    if (tb.expire_slots[i] == slot) days = tb.expire_days[i];
-  return days;
-}
-
-// One shard of one table: buckets [begin, end) of partial_dump (cuckoohash_map.hpp:740-773), in
-// chunks; rows expired relative to the table's max_update_ts are dropped
-// (multi_hash_table_save_restore_ops.cc:203-211).  Returns the number of entries written.
-static uint64_t save_table_shard(Table& tb, int shard, int total, ckpt::RecordWriter& w,
-                                 CkptStage& sg, hipStream_t st) {
-  // the shard's bucket range is a function of the hashpower: a doubling between two chunks (a
-  // concurrent update: the table is released between chunks) would leave the rest of the range
-  // stale — rows missed or written twice.  The geometry is snapshotted under the lock and checked
-  // by every chunk's scan; a change fails the save (the reference holds LockAll for the whole save,
-  // hash_table_save_op.cc:106-108).
-  uint32_t hp0;
-  {
-    std::lock_guard<std::mutex> g(tb.mu);
-    hp0 = tb.hp;
-  }
-  const uint64_t nb = uint64_t(1) << hp0;
-  const uint64_t Q = nb / uint64_t(total), R = nb % uint64_t(total);
-  const uint64_t begin = uint64_t(shard) * Q + std::min<uint64_t>(shard, R);
-  const uint64_t end = begin + Q + (uint64_t(shard) < R ? 1 : 0);
-  const std::vector<ckpt::SegLayout> segs = seg_layout(tb);
-  const uint32_t rf = tb.row_floats;
-  // chunk = what one pipeline stage holds at a time: small enough that a shard has several of them
-  // in flight (scan | encode | write beside each other) and that the two pinned staging sets stay
-  // in the hundreds of megabytes, large enough that the per-chunk synchronisations do not show
-  const uint64_t kChunkSlots = uint64_t(1) << 18;
-  DevBuf<uint32_t>& bc = sg.bc;
-  DevBuf<uint64_t>& bo = sg.bo;
-  DevBuf<int64_t>&d_ids = sg.d_ids, &d_pos = sg.d_pos;
-  DevBuf<uint32_t>& d_ts = sg.d_ts;
-  DevBuf<float>& d_rows = sg.d_rows;
-  std::string rec;
-  uint64_t written = 0;
-  auto expired = [&](int64_t id, uint32_t ts) {
-    return tb.max_update_ts - int64_t(ts) >= ttl_days_of(tb, id) * int64_t(86400);
-  };
-  auto emit = [&](int64_t id, const float* row, uint32_t ts) {
-    if (expired(id, ts)) return;
-    ckpt::encode_entry(rec, id, row, segs, int(tb.dim), ts);
-    w.write(rec);
-    ++written;
-  };
-  const int P = ckpt_codec_threads();
-  for (int b = 0; b < 2; ++b) {
-    if (sg.parts[b].size() < size_t(P)) sg.parts[b].resize(size_t(P));
-    sg.part_n[b].assign(size_t(P), 0);
-    sg.h_n[b] = 0;
-  }
-  const bool trace = getenv("MHTE_CKPT_TRACE") != nullptr;   // phase seconds of this shard to stderr
-  double t_scan = 0, t_enc = 0, t_write = 0;                 // (each written by its stage's thread only)
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const uint64_t slot_begin = begin * kSlots, slot_end = end * kSlots;
-  const size_t n_chunks = size_t((slot_end - slot_begin + kChunkSlots - 1) / kChunkSlots);
-  // stage A (this thread: it owns the HIP stream): device scan of the chunk's slots + copy of the
-  // rows it found into pinned set b.  The table is held for that only; the (longer) encoding and
-  // writing of the chunk run beside the next chunk's scan and the other shards' threads.
-  auto scan = [&](size_t c, int b) {
-    const double t0 = now();
-    const uint64_t s0 = slot_begin + uint64_t(c) * kChunkSlots;
-    const uint64_t s1 = std::min(slot_end, s0 + kChunkSlots);
-    const uint32_t nblocks = uint32_t((s1 - s0 + 1023) / 1024);
-    uint64_t acc = 0;
-    sg.h_n[b] = 0;
-    std::lock_guard<std::mutex> g(tb.mu);
-    if (tb.hp != hp0)
-      throw Error(MHTE_FAILED_PRECONDITION, "table " + tb.name + " was resized by a concurrent update while "
-                                            "it was being saved; save again");
-    bc.reserve(nblocks);
-    bo.reserve(nblocks);
-    dump_count_kernel<<<nblocks, 256, 0, st>>>(tb.view, s0, s1, bc.p);
-    HIP_OK(hipGetLastError());
-    std::vector<uint32_t> hc(nblocks);
-    HIP_OK(hipMemcpyAsync(hc.data(), bc.p, sizeof(uint32_t) * nblocks, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    std::vector<uint64_t> ho(nblocks);
-    for (uint32_t i = 0; i < nblocks; ++i) {
-      ho[i] = acc;
-      acc += hc[i];
-    }
-    if (acc != 0) {
-      d_ids.reserve(acc);
-      d_pos.reserve(acc);
-      d_ts.reserve(acc);
-      d_rows.reserve(acc * rf);
-      HIP_OK(hipMemcpyAsync(bo.p, ho.data(), sizeof(uint64_t) * nblocks, hipMemcpyHostToDevice, st));
-      dump_emit_kernel<<<nblocks, 256, 0, st>>>(tb.view, s0, s1, bo.p, d_ids.p, d_pos.p, d_ts.p, d_rows.p);
-      HIP_OK(hipGetLastError());
-      sg.h_ids[b].reserve(acc);
-      sg.h_ts[b].reserve(acc);
-      sg.h_rows[b].reserve(acc * rf);
-      HIP_OK(hipMemcpyAsync(sg.h_ids[b].p, d_ids.p, acc * 8, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(sg.h_ts[b].p, d_ts.p, acc * 4, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(sg.h_rows[b].p, d_rows.p, acc * rf * 4, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      sg.h_n[b] = acc;
-    }
-    t_scan += now() - t0;
-  };
-  // stage B: EntryDump + TFRecord framing of the chunk's rows on P threads (contiguous ranges, so
-  // the file keeps the dump order) into set b's strings
-  auto encode = [&](size_t, int b) {
-    const double t0 = now();
-    const uint64_t acc = sg.h_n[b];
-    const int64_t* ids = sg.h_ids[b].p;
-    const uint32_t* tsv = sg.h_ts[b].p;
-    const float* rows = sg.h_rows[b].p;
-    std::vector<std::string>& parts = sg.parts[b];
-    std::vector<uint64_t>& part_n = sg.part_n[b];
-    for (int k = 0; k < P; ++k) {
-      parts[size_t(k)].clear();
-      part_n[size_t(k)] = 0;
-    }
-    if (acc)
-      parallel_ranges(size_t(acc), P, [&](size_t lo, size_t hi, int k) {
-        std::string& out = parts[size_t(k)];
-        std::string r;
-        uint64_t n = 0;
-        for (size_t i = lo; i < hi; ++i) {
-          if (expired(ids[i], tsv[i])) continue;
-          ckpt::encode_entry(r, ids[i], rows + i * rf, segs, int(tb.dim), tsv[i]);
-          ckpt::RecordWriter::frame(out, r);
-          ++n;
-        }
-        part_n[size_t(k)] = n;
-      });
-    t_enc += now() - t0;
-  };
-  // stage C: the framed bytes through the writer, in range order
-  auto write_out = [&](size_t, int b) {
-    const double t0 = now();
-    for (int k = 0; k < P; ++k) {
-      if (sg.parts[b][size_t(k)].empty()) continue;
-      w.write_framed(sg.parts[b][size_t(k)]);
-      written += sg.part_n[b][size_t(k)];
-    }
-    t_write += now() - t0;
-  };
-  const double t_pipe0 = now();
-  ckpt::run_pipeline3(n_chunks, scan, encode, write_out);
-  if (trace)
-    fprintf(stderr, "[mhte ckpt] save %s shard %d/%d: %llu rows in %zu chunks, %.3f s (stage seconds, "
-                    "overlapped: scan+copy %.3f, encode(%d thr) %.3f, write %.3f)\n", tb.name.c_str(), shard,
-            total, (unsigned long long)written, n_chunks, now() - t_pipe0, t_scan, P, t_enc, t_write);
-  if (shard == 0 && tb.h_ctr->special_state == 1) {
-    std::lock_guard<std::mutex> g(tb.mu);
-    // the one key that lives in the side slot (kEmptyKey itself): last entry of shard 0
-    std::vector<float> row(rf);
-    Counters c;
-    HIP_OK(hipMemcpy(&c, tb.ctr, sizeof(Counters), hipMemcpyDeviceToHost));
-    const uint32_t r = c.special_row;
-    const uint32_t ch = r >> tb.chunk_shift;
-    const float* src = tb.chunks[ch] + size_t(r & ((1u << tb.chunk_shift) - 1u)) * rf;
-    HIP_OK(hipMemcpy(row.data(), src, rf * 4, hipMemcpyDeviceToHost));
-    emit(kEmptyKey, row.data(), c.special_ts);
-  }
-  return written;
-}
-
-// shard jobs 0..n-1 on at most 16 host threads (the caller's included); jobs catch their own errors
-template <typename F>
-static void run_shard_jobs(int n, F&& job) {
-  std::atomic<int> next{0};
-  auto worker = [&] {
-    for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) job(i);
-  };
-  std::vector<std::thread> th;
-  const int extra = std::min(n, 16) - 1;
-  for (int i = 0; i < extra; ++i) th.emplace_back(worker);
-  worker();
-  for (auto& x : th) x.join();
-}
-
-static void save_multi_table(mhte_multi_table* t, const std::string& basename, int nshards,
-                             hipStream_t st) {
-  int64_t total = 0;
-  for (auto& tb : t->tables) {
-    std::lock_guard<std::mutex> g(tb->mu);
-    tb->sync_counters(st);
-    total += tb->live_keys() + (tb->h_ctr->special_state == 1 ? 1 : 0);
-  }
-  // PickNshards, multi_hash_table_save_restore_ops.cc:240-248
-  if (nshards < 0) nshards = int(std::min<int64_t>(4, std::max<int64_t>(1, total / 1000000)));
-  if (nshards < 1) nshards = 1;
-  // one thread per shard (the reference schedules its shards on the op's thread pool,
-  // multi_hash_table_save_restore_ops.cc:250-262), each with a stream of its own
-  HIP_OK(hipStreamSynchronize(st));
-  std::vector<std::exception_ptr> err;
-  err.resize(size_t(nshards));
-  const bool trace = getenv("MHTE_CKPT_TRACE") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = now();
-  auto shard_job = [&](int sh) {
-    hipStream_t s2 = nullptr;
-    const double tj0 = now();
-    try {
-      HIP_OK(hipSetDevice(t->device));
-      HIP_OK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-      const std::string fn = ckpt::shard_name(basename, "", sh, nshards);
-      const std::string mfn = ckpt::shard_name(basename, ".meta", sh, nshards);
-      const std::string tmp = fn + "-tmp-" + std::to_string(uint64_t(getpid())) + "-" + std::to_string(sh);
-      const std::string mtmp = mfn + "-tmp-" + std::to_string(uint64_t(getpid())) + "-" + std::to_string(sh);
-      {
-        ckpt::RecordWriter w(tmp, true), mw(mtmp, false);
-        std::string meta;
-        const double tj1 = now();
-        std::unique_ptr<CkptStage> sg = t->take_stage();
-        try {
-          for (auto& tb : t->tables) {
-            const uint64_t n = save_table_shard(*tb, sh, nshards, w, *sg, s2);
-            ckpt::encode_meta(meta, tb->name, n);
-            mw.write(meta);
-          }
-        } catch (...) {
-          t->give_stage(std::move(sg));
-          throw;
-        }
-        t->give_stage(std::move(sg));
-        const double tj2 = now();
-        w.close();
-        mw.close();
-        if (trace)
-          fprintf(stderr, "[mhte ckpt] save shard %d: started +%.3f s, setup %.3f s, tables %.3f s, close %.3f s\n",
-                  sh, tj0 - t_begin, tj1 - tj0, tj2 - tj1, now() - tj2);
-      }
-      if (rename(tmp.c_str(), fn.c_str()) != 0 || rename(mtmp.c_str(), mfn.c_str()) != 0)
-        throw Error(MHTE_INTERNAL, "checkpoint: cannot rename into " + fn);
-    } catch (...) {
-      err[size_t(sh)] = std::current_exception();
-    }
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  run_shard_jobs(nshards, shard_job);
-  if (trace) fprintf(stderr, "[mhte ckpt] save: all shards done +%.3f s\n", now() - t_begin);
-  for (auto& e : err)
-    if (e) std::rethrow_exception(e);
-}
-
-// rows of one restore batch -> table (upsert of whole rows with their own timestamps)
-static void restore_batch(Table& tb, CkptStage& sg, const int64_t* ids, const float* rows,
-                          const uint32_t* ts, int64_t n, hipStream_t st) {
-  if (n == 0) return;
-  tb.finish_pending(st);
-  ++tb.mut_epoch;
-  tb.ensure_capacity(uint64_t(n), st);
-  sg.d_ids.reserve(size_t(n));
-  sg.d_ts.reserve(size_t(n));
-  sg.d_rows.reserve(size_t(n) * tb.row_floats);
-  HIP_OK(hipMemcpyAsync(sg.d_ids.p, ids, n * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(sg.d_ts.p, ts, n * 4, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(sg.d_rows.p, rows, size_t(n) * tb.row_floats * 4, hipMemcpyHostToDevice, st));
-  tb.pending.reserve(size_t(n) + 1);
-  const dim3 grid(uint32_t((n * 16 + 255) / 256));
-  restore_rows_kernel<16><<<grid, 256, 0, st>>>(tb.view, sg.d_ids.p, n, sg.d_rows.p, sg.d_ts.p, tb.pending.p);
-  restore_slowpath_kernel<<<1, 64, 0, st>>>(tb.view, sg.d_ids.p, sg.d_rows.p, sg.d_ts.p, tb.pending.p);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(st));  // the staging buffers are rewritten by the next batch
-}
-
-// legacy_table >= 0: the single-table layout of MonolithHashTableSave (hash_table_save_op.cc:147-160) —
-// an UNCOMPRESSED TFRecord stream of EntryDump, no .meta sidecar: every record of the file belongs to
-// that table (hash_table_restore_op.cc:118-150)
-static void restore_shard(mhte_multi_table* t, const std::string& basename, int sh, int total,
-                          hipStream_t st, int legacy_table = -1) {
-  {
-    const bool legacy = legacy_table >= 0;
-    ckpt::RecordReader data(ckpt::shard_name(basename, "", sh, total), !legacy);
-    std::unique_ptr<ckpt::RecordReader> meta;
-    if (!legacy) meta.reset(new ckpt::RecordReader(ckpt::shard_name(basename, ".meta", sh, total), false));
-    std::string mrec, name;
-    // the data file is read in stretches of ~64 MiB into the stage's arena; `refs[cur..)` are the
-    // records of the current stretch not yet consumed (a stretch may span two tables)
-    std::unique_ptr<CkptStage> sgp = t->take_stage();
-    struct Return {
-      mhte_multi_table* t;
-      std::unique_ptr<CkptStage>& s;
-      ~Return() { t->give_stage(std::move(s)); }
-    } give_back{t, sgp};
-    CkptStage& sg = *sgp;
-    // Two stretches: while the records of one are verified, decoded and upserted, a helper thread
-    // reads and unpacks the next one (the reader is only ever used by that one thread at a time).
-    std::vector<ckpt::RecordReader::RecRef> refs_buf[2];
-    int use = 0;                      // stretch in use: sg.arena[use], refs_buf[use]
-    size_t cur = 0;
-    const size_t kStretch = size_t(64) << 20;
-    // the snappy blocks of a stretch are unpacked side by side on a few threads of the reader's own
-    const int kUnpackThreads = std::min(4, ckpt_codec_threads());
-    const ckpt::ParallelFor unpack = [kUnpackThreads](size_t n, const std::function<void(size_t, size_t)>& fn) {
-      parallel_ranges(n, kUnpackThreads, [&](size_t lo, size_t hi, int) { fn(lo, hi); });
-    };
-    std::future<bool> ahead;          // the read into the other stretch
-    auto read_into = [&](int b) {
-      ahead = std::async(std::launch::async,
-                         [&, b] { return data.read_batch(sg.arena[b], kStretch, refs_buf[b], unpack); });
-    };
-    struct Drain {                    // never leave the helper running into freed buffers
-      std::future<bool>& f;
-      ~Drain() {
-        if (f.valid()) {
-          try {
-            (void)f.get();
-          } catch (...) {
-          }
-        }
-      }
-    } drain{ahead};
-    read_into(0);
-    bool started = false, at_end = false;
-    size_t avail = 0;   // records of the stretch in use (this thread's view: the helper may be
-                        // filling the other stretch's vectors right now)
-    // up to `want` records of the stream -> (first, count) in refs_buf[use]; 0 at the end of the file
-    auto take = [&](uint64_t want, size_t* first) -> size_t {
-      if (cur == avail) {
-        if (at_end) return 0;
-        const int nxt = started ? (use ^ 1) : 0;
-        const bool got = ahead.get();          // (rethrows the reader's errors)
-        started = true;
-        use = nxt;
-        cur = 0;
-        avail = got ? refs_buf[use].size() : 0;
-        if (!got) {
-          at_end = true;
-          return 0;
-        }
-        read_into(use ^ 1);
-      }
-      const size_t k = size_t(std::min<uint64_t>(want, avail - cur));
-      *first = cur;
-      cur += k;
-      return k;
-    };
-    bool legacy_done = false;
-    for (;;) {
-      uint64_t num = 0;
-      int idx = -1;
-      if (legacy) {
-        if (legacy_done) break;
-        legacy_done = true;
-        idx = legacy_table;
-        name = t->tables[size_t(idx)]->name;
-        num = ~uint64_t(0);   // until the end of the file
-      } else {
-        if (!meta->read(&mrec)) break;
-        ckpt::decode_meta(reinterpret_cast<const uint8_t*>(mrec.data()), mrec.size(), &name, &num);
-        for (size_t i = 0; i < t->tables.size(); ++i)
-          if (t->tables[i]->name == name) idx = int(i);
-      }
-      if (idx < 0) {  // table in the checkpoint but not in this MultiHashTable: skipped (:352-361)
-        for (uint64_t left = num; left;) {
-          size_t first;
-          const size_t k = take(left, &first);
-          if (!k) throw Error(MHTE_INTERNAL, "checkpoint shard ends early");
-          left -= k;
-        }
-        continue;
-      }
-      Table& tb = *t->tables[size_t(idx)];
-      // (layout and initial values are fixed at creation: read without the table's lock)
-      const std::vector<ckpt::SegLayout> segs = seg_layout(tb);
-      const uint32_t rf = tb.row_floats;
-      // a row starts from initializer + optimizer Init (UpsertEntry's init_fn), then the dump
-      // overwrites what it carries
-      std::vector<float> init(rf, 0.f);
-      for (uint32_t k = 0; k < tb.nseg; ++k) {
-        const SegDesc& d = tb.view.seg[k];
-        // (a dump always carries `num`: the initial weight only stands in until it is overwritten)
-        const float w0 = d.init == kInitRandomUniform ? 0.f : init_weight(d, nullptr);
-        const int nv = opt_vectors(d.opt);
-        for (int e = 0; e < d.dim; ++e) {
-          init[size_t(d.w_off + e)] = w0;
-          for (int v2 = 0; v2 < nv; ++v2) init[size_t(d.st_off + v2 * d.dim + e)] = opt_state_init(d, v2);
-        }
-        if (opt_scalars(d.opt)) {  // adam_optimizer.cc:52-53
-          init[size_t(d.st_off + nv * d.dim)] = d.p[0];
-          init[size_t(d.st_off + nv * d.dim + 1)] = d.p[1];
-        }
-        if (d.opt == kOptGroupAdagrad) init[size_t(d.st_off)] = d.p[0];  // group_adagrad_optimizer.cc:45-48
-      }
-      const size_t kBatch = size_t(1) << 18;
-      const int P = ckpt_codec_threads();
-      std::vector<int64_t> part_max(static_cast<size_t>(P), 0);
-      const bool trace = getenv("MHTE_CKPT_TRACE") != nullptr;
-      double t_read = 0, t_dec = 0, t_up = 0;   // (read / decode: this thread; upsert: the helper)
-      auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-      // Two stages beside each other over the table's batches (ckpt::run_pipeline3, two staging
-      // sets): this thread takes the next records of the stream and verifies + decodes them on P
-      // threads into pinned set b; a helper checks the batch for repeated ids and upserts it.
-      uint64_t done = 0;
-      size_t set_n[2] = {0, 0};
-      int64_t set_max_ts[2] = {0, 0};
-      auto decode = [&](size_t, int b) -> bool {
-        if (done >= num) return false;
-        // the file is read in order (one reader per shard); a batch's records are verified (data
-        // crc) and decoded in place, on P threads
-        const double t0 = now();
-        size_t first = 0;
-        const size_t nb = take(std::min<uint64_t>(kBatch, num - done), &first);
-        if (!nb) {
-          if (legacy) return false;
-          throw Error(MHTE_INTERNAL, "checkpoint shard ends early");
-        }
-        const double t1 = now();
-        HostBuf<int64_t>& ids = sg.h_ids[b];
-        HostBuf<uint32_t>& ts = sg.h_ts[b];
-        HostBuf<float>& rows = sg.h_rows[b];
-        ids.reserve(nb);
-        ts.reserve(nb);
-        rows.reserve(nb * rf);
-        const char* base = sg.arena[use].data();
-        const std::vector<ckpt::RecordReader::RecRef>& refs = refs_buf[use];
-        parallel_ranges(nb, P, [&](size_t lo, size_t hi, int k) {
-          int64_t mx = 0;
-          for (size_t i = lo; i < hi; ++i) {
-            const ckpt::RecordReader::RecRef& r = refs[first + i];
-            data.verify(base + r.off, r.len, r.crc);
-            float* row = rows.p + i * rf;
-            memcpy(row, init.data(), sizeof(float) * rf);
-            int64_t id;
-            uint32_t tsv;
-            ckpt::decode_entry(reinterpret_cast<const uint8_t*>(base + r.off), r.len, segs, int(tb.dim),
-                               &id, row, &tsv);
-            ids.p[i] = id;
-            ts.p[i] = tsv;
-            mx = std::max<int64_t>(mx, int64_t(tsv));
-          }
-          part_max[size_t(k)] = mx;
-        });
-        int64_t max_ts = 0;
-        for (int k = 0; k < P; ++k) {
-          max_ts = std::max(max_ts, part_max[size_t(k)]);
-          part_max[size_t(k)] = 0;
-        }
-        set_n[b] = nb;
-        set_max_ts[b] = max_ts;
-        done += nb;
-        t_read += t1 - t0;
-        t_dec += now() - t1;
-        return true;
-      };
-      std::vector<uint32_t> seen;   // open-addressing set of the batch's ids: index + 1, 0 = free
-      auto upsert = [&](size_t, int b) {
-        const double t0 = now();
-        HIP_OK(hipSetDevice(t->device));   // (a thread of the pipeline's own)
-        const size_t nb = set_n[b];
-        const int64_t* ids = sg.h_ids[b].p;
-        // ids inside one upsert launch must be distinct.  A checkpoint holds each id once per table,
-        // but a foreign writer (or concatenated files) may repeat one: the reference upserts entry
-        // after entry, so the LATER record wins (cuckoo_embedding_hash_table.cc:303-318).  The batch
-        // is therefore applied as maximal runs of distinct ids, one launch per run, in file order.
-        size_t cap = 1024;
-        while (cap < 2 * nb) cap <<= 1;
-        size_t start = 0;
-        while (start < nb) {
-          seen.assign(cap, 0u);
-          size_t end = start;
-          for (; end < nb; ++end) {
-            size_t h = size_t(hash_key(ids[end])) & (cap - 1);
-            bool dup = false;
-            while (seen[h]) {
-              if (ids[seen[h] - 1] == ids[end]) {
-                dup = true;
-                break;
-              }
-              h = (h + 1) & (cap - 1);
-            }
-            if (dup) break;
-            seen[h] = uint32_t(end + 1);
-          }
-          std::lock_guard<std::mutex> g(tb.mu);
-          tb.max_update_ts = std::max<int64_t>(tb.max_update_ts, set_max_ts[b]);
-          restore_batch(tb, sg, ids + start, sg.h_rows[b].p + start * rf, sg.h_ts[b].p + start,
-                        int64_t(end - start), st);
-          start = end;
-        }
-        t_up += now() - t0;
-      };
-      ckpt::run_pipeline3(size_t(-1), decode, upsert, [](size_t, int) {});
-      if (trace)
-        fprintf(stderr, "[mhte ckpt] restore %s shard %d/%d: %llu rows, read %.3f s, verify+decode(%d thr) "
-                        "%.3f s | dup check + upsert %.3f s (beside each other)\n", name.c_str(), sh, total,
-                (unsigned long long)num, t_read, P, t_dec, t_up);
-    }
-    size_t first = 0;
-    if (take(1, &first)) throw Error(MHTE_INTERNAL, "Couldn't read all of checkpoint shard");
-  }
-}
-
-// The shard set of a checkpoint: what the directory holds under <basename>-%05d-of-%05d (the
-// reference globs <basename>-* and validates the set, ValidateShardedFiles,
-// multi_hash_table_save_restore_ops.cc:323-349): one consistent total, every data shard and every
-// .meta sidecar present.  Leftovers of an earlier save with another shard count are an error, not
-// something to restore silently.
-static int discover_shards(const std::string& basename, bool want_meta = true) {
-  int total = 0;
-  {
-    const size_t slash = basename.find_last_of('/');
-    const std::string dir = slash == std::string::npos ? "." : basename.substr(0, slash == 0 ? 1 : slash);
-    const std::string stem = slash == std::string::npos ? basename : basename.substr(slash + 1);
-    std::vector<std::pair<int, int>> data, meta;  // (index, total)
-    DIR* dp = opendir(dir.c_str());
-    if (!dp) throw Error(MHTE_NOT_FOUND, "no checkpoint shards found for " + basename);
-    while (dirent* de = readdir(dp)) {
-      const std::string fn = de->d_name;
-      for (int is_meta = 0; is_meta < 2; ++is_meta) {
-        const std::string pre = stem + (is_meta ? ".meta-" : "-");
-        if (fn.size() != pre.size() + 14 || fn.compare(0, pre.size(), pre) != 0) continue;
-        const std::string tail = fn.substr(pre.size());  // ddddd-of-ddddd
-        if (tail.compare(5, 4, "-of-") != 0) continue;
-        bool digits = true;
-        for (int k = 0; k < 14; ++k)
-          if (k < 5 || k >= 9) digits = digits && isdigit(static_cast<unsigned char>(tail[k]));
-        if (!digits) continue;
-        (is_meta ? meta : data).emplace_back(atoi(tail.substr(0, 5).c_str()), atoi(tail.substr(9).c_str()));
-      }
-    }
-    closedir(dp);
-    if (data.empty()) throw Error(MHTE_NOT_FOUND, "no checkpoint shards found for " + basename);
-    total = data[0].second;
-    auto complete = [&](std::vector<std::pair<int, int>>& v, const char* what) {
-      std::sort(v.begin(), v.end());
-      bool ok = int(v.size()) == total;
-      for (int i = 0; ok && i < total; ++i) ok = v[size_t(i)].first == i && v[size_t(i)].second == total;
-      if (!ok)
-        throw Error(MHTE_INVALID_ARGUMENT,
-                    std::string("checkpoint ") + basename + ": the " + what + " files are not one "
-                    "complete set of -%05d-of-%05d shards (stale files of another save?)");
-    };
-    complete(data, "data");
-    if (want_meta) complete(meta, ".meta");
-  }
-  return total;
-}
-
-static void restore_multi_table(mhte_multi_table* t, const std::string& basename, hipStream_t st) {
-  const int total = discover_shards(basename);
-  // one thread per shard file: decoding (the long part) runs in parallel, a table is held only
-  // while a decoded batch is upserted
-  HIP_OK(hipStreamSynchronize(st));
-  std::vector<std::exception_ptr> err;
-  err.resize(size_t(total));
-  auto shard_job = [&](int sh) {
-    hipStream_t s2 = nullptr;
-    try {
-      HIP_OK(hipSetDevice(t->device));
-      HIP_OK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-      restore_shard(t, basename, sh, total, s2);
-    } catch (...) {
-      err[size_t(sh)] = std::current_exception();
-    }
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  run_shard_jobs(total, shard_job);
-  for (auto& e : err)
-    if (e) std::rethrow_exception(e);
-}
-
-// MonolithHashTableSave for ONE table (hash_table_save_op.cc:98-173): per shard an uncompressed
-// TFRecord file of EntryDump over a contiguous bucket range, written under a temporary name and
-// renamed; rows expired relative to the table's max_update_ts are left out (:149-155).
-static void save_table_legacy(mhte_multi_table* t, int idx, const std::string& basename, int nshards,
-                              hipStream_t st) {
-  Table& tbl = *t->tables[size_t(idx)];
-  int64_t total = 0;
-  {
-    std::lock_guard<std::mutex> g(tbl.mu);
-    tbl.sync_counters(st);
-    total = tbl.live_keys() + (tbl.h_ctr->special_state == 1 ? 1 : 0);
-  }
-  if (nshards < 0) nshards = int(std::min<int64_t>(4, std::max<int64_t>(1, total / 1000000)));   // PickNshards :122-127
-  if (nshards < 1) nshards = 1;
-  HIP_OK(hipStreamSynchronize(st));
-  std::vector<std::exception_ptr> err;
-  err.resize(size_t(nshards));
-  auto shard_job = [&](int sh) {
-    hipStream_t s2 = nullptr;
-    try {
-      HIP_OK(hipSetDevice(t->device));
-      HIP_OK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-      const std::string fn = ckpt::shard_name(basename, "", sh, nshards);
-      const std::string tmp = fn + "-tmp-" + std::to_string(uint64_t(getpid())) + "-" + std::to_string(sh);
-      {
-        ckpt::RecordWriter w(tmp, false);
-        std::unique_ptr<CkptStage> sg = t->take_stage();
-        try {
-          (void)save_table_shard(tbl, sh, nshards, w, *sg, s2);
-        } catch (...) {
-          t->give_stage(std::move(sg));
-          throw;
-        }
-        t->give_stage(std::move(sg));
-        w.close();
-      }
-      if (rename(tmp.c_str(), fn.c_str()) != 0) throw Error(MHTE_INTERNAL, "checkpoint: cannot rename into " + fn);
-    } catch (...) {
-      err[size_t(sh)] = std::current_exception();
-    }
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  run_shard_jobs(nshards, shard_job);
-  for (auto& e : err)
-    if (e) std::rethrow_exception(e);
-}
-
-// MonolithHashTableRestore for ONE table (hash_table_restore_op.cc:67-100): the shard set is
-// validated (ValidateShardedFiles), the table is CLEARED, then every shard's records are upserted.
-static void restore_table_legacy(mhte_multi_table* t, int idx, const std::string& basename, hipStream_t st) {
-  const int total = discover_shards(basename, false);
-  Table& tbl = *t->tables[size_t(idx)];
-  {
-    std::lock_guard<std::mutex> g(tbl.mu);
-    tbl.clear(st);
-  }
-  HIP_OK(hipStreamSynchronize(st));
-  std::vector<std::exception_ptr> err;
-  err.resize(size_t(total));
-  auto shard_job = [&](int sh) {
-    hipStream_t s2 = nullptr;
-    try {
-      HIP_OK(hipSetDevice(t->device));
-      HIP_OK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-      restore_shard(t, basename, sh, total, s2, idx);
-    } catch (...) {
-      err[size_t(sh)] = std::current_exception();
-    }
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  run_shard_jobs(total, shard_job);
-  for (auto& e : err)
-    if (e) std::rethrow_exception(e);
-}
-
-}  // namespace mhte
-}  // extern "C++"
-
+// ---- checkpoints in the reference's on-disk format (mhte_ckpt_host.h) ---------------------------
 mhte_status mhte_multi_table_save(mhte_multi_table* t, const char* basename, int32_t nshards,
                                   void* stream) {
   return guard([&] {
     check_handle(t);
-    if (!basename || !*basename) throw Error(MHTE_INVALID_ARGUMENT, "save: empty basename");
-    HIP_OK(hipSetDevice(t->device));
-    try {
-      save_multi_table(t, basename, nshards, S(stream));
-    } catch (const Error&) {
-      throw;
-    } catch (const std::exception& e) {
-      throw Error(MHTE_INTERNAL, e.what());
-    }
+    ckpt_entry(t, false, basename, [&] { save_tables(t, basename, nshards, S(stream)); });
   });
 }
 
 mhte_status mhte_multi_table_restore(mhte_multi_table* t, const char* basename, void* stream) {
   return guard([&] {
     check_handle(t);
-    if (!basename || !*basename) throw Error(MHTE_INVALID_ARGUMENT, "restore: empty basename");
-    HIP_OK(hipSetDevice(t->device));
-    try {
-      restore_multi_table(t, basename, S(stream));
-    } catch (const Error&) {
-      throw;
-    } catch (const std::exception& e) {
-      throw Error(MHTE_INTERNAL, std::string("DataLoss: ") + e.what());
-    }
+    ckpt_entry(t, true, basename, [&] { restore_tables(t, basename, S(stream)); });
   });
 }
 
 mhte_status mhte_table_save(mhte_multi_table* t, int32_t table, const char* basename, int32_t nshards,
                             void* stream) {
   return guard([&] {
-    check_handle(t);
-    if (table < 0 || size_t(table) >= t->tables.size()) throw Error(MHTE_INVALID_ARGUMENT, "table index out of range");
-    if (!basename || !*basename) throw Error(MHTE_INVALID_ARGUMENT, "save: empty basename");
-    HIP_OK(hipSetDevice(t->device));
-    try {
-      save_table_legacy(t, table, basename, nshards, S(stream));
-    } catch (const Error&) {
-      throw;
-    } catch (const std::exception& e) {
-      throw Error(MHTE_INTERNAL, e.what());
-    }
+    table_at(t, table);
+    ckpt_entry(t, false, basename, [&] { save_tables(t, basename, nshards, S(stream), table); });
   });
 }
 
 mhte_status mhte_table_restore(mhte_multi_table* t, int32_t table, const char* basename, void* stream) {
   return guard([&] {
-    check_handle(t);
-    if (table < 0 || size_t(table) >= t->tables.size()) throw Error(MHTE_INVALID_ARGUMENT, "table index out of range");
-    if (!basename || !*basename) throw Error(MHTE_INVALID_ARGUMENT, "restore: empty basename");
-    HIP_OK(hipSetDevice(t->device));
-    try {
-      restore_table_legacy(t, table, basename, S(stream));
-    } catch (const Error&) {
-      throw;
-    } catch (const std::exception& e) {
-      throw Error(MHTE_INTERNAL, std::string("DataLoss: ") + e.what());
-    }
+    table_at(t, table);
+    ckpt_entry(t, true, basename, [&] { restore_tables(t, basename, S(stream), table); });
   });
 }
 
 mhte_status mhte_table_clear(mhte_multi_table* t, int32_t table, void* stream) {
   return guard([&] {
-    check_handle(t);
-    if (table < 0 || size_t(table) >= t->tables.size()) throw Error(MHTE_INVALID_ARGUMENT, "table index out of range");
+    Table& tb = table_at(t, table);
     HIP_OK(hipSetDevice(t->device));
-    Table& tb = *t->tables[size_t(table)];
     std::lock_guard<std::mutex> g(tb.mu);
     tb.clear(S(stream));
   });
@@ -5501,149 +4708,14 @@ mhte_status mhte_table_save_as_tensor(mhte_multi_table* t, int32_t table, int32_
                                       char* entries, int64_t cap, int64_t* entry_offsets,
                                       int64_t offsets_cap, int64_t* n_entries, int64_t* needed, void* stream) {
   return guard([&] {
-    Table& tb = table_at(t, table);
-    if (!new_offset || !n_entries || !needed) throw Error(MHTE_INVALID_ARGUMENT, "save_as_tensor: null argument");
-    if (num_shards < 1 || shard_idx < 0 || shard_idx >= num_shards || offset < 0)
-      throw Error(MHTE_INVALID_ARGUMENT, "save_as_tensor: shard " + std::to_string(shard_idx) + " of " +
-                                             std::to_string(num_shards) + ", offset " + std::to_string(offset));
-    HIP_OK(hipSetDevice(t->device));
-    hipStream_t st = S(stream);
-    std::lock_guard<std::mutex> g(tb.mu);
-    tb.finish_pending(st);
-    // cuckoohash_map.hpp:745-773: the shard's bucket range, the resume point inside it, at most `limit`
-    // entries (the count is checked AFTER an entry is taken: limit <= 0 still yields one)
-    const uint64_t hash_size = uint64_t(1) << tb.hp;
-    const uint64_t Q = hash_size / uint64_t(num_shards), R = hash_size % uint64_t(num_shards);
-    const uint64_t begin = uint64_t(shard_idx) * Q + std::min<uint64_t>(uint64_t(shard_idx), R);
-    const uint64_t end = begin + Q + (uint64_t(shard_idx) < R ? 1 : 0);
-    const uint64_t want = uint64_t(std::max<int64_t>(limit, 1));
-    const uint64_t s_end = end * kSlots;
-    uint64_t s0 = begin * kSlots + uint64_t(offset);
-    const size_t rf = tb.row_floats;
-    std::vector<int64_t> ids;
-    std::vector<int64_t> pos;
-    std::vector<uint32_t> ts;
-    std::vector<float> rows;
-    DevBuf<uint32_t> bc;
-    DevBuf<uint64_t> bo;
-    DevBuf<int64_t> d_ids, d_pos;
-    DevBuf<uint32_t> d_ts;
-    DevBuf<float> d_rows;
-    constexpr uint64_t kChunk = uint64_t(1) << 18;
-    while (s0 < s_end && ids.size() < want) {
-      const uint64_t s1 = std::min(s_end, s0 + kChunk);
-      const uint32_t nblocks = uint32_t((s1 - s0 + 1023) / 1024);
-      bc.reserve(nblocks);
-      bo.reserve(nblocks);
-      dump_count_kernel<<<nblocks, 256, 0, st>>>(tb.view, s0, s1, bc.p);
-      HIP_OK(hipGetLastError());
-      std::vector<uint32_t> hc(nblocks);
-      HIP_OK(hipMemcpyAsync(hc.data(), bc.p, sizeof(uint32_t) * nblocks, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      std::vector<uint64_t> ho(nblocks);
-      uint64_t acc = 0;
-      for (uint32_t i = 0; i < nblocks; ++i) {
-        ho[i] = acc;
-        acc += hc[i];
-      }
-      if (acc) {
-        d_ids.reserve(acc);
-        d_pos.reserve(acc);
-        d_ts.reserve(acc);
-        d_rows.reserve(acc * rf);
-        HIP_OK(hipMemcpyAsync(bo.p, ho.data(), sizeof(uint64_t) * nblocks, hipMemcpyHostToDevice, st));
-        dump_emit_kernel<<<nblocks, 256, 0, st>>>(tb.view, s0, s1, bo.p, d_ids.p, d_pos.p, d_ts.p, d_rows.p);
-        HIP_OK(hipGetLastError());
-        const size_t take = size_t(std::min<uint64_t>(acc, want - ids.size())), at = ids.size();
-        ids.resize(at + take);
-        pos.resize(at + take);
-        ts.resize(at + take);
-        rows.resize((at + take) * rf);
-        HIP_OK(hipMemcpyAsync(ids.data() + at, d_ids.p, take * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(pos.data() + at, d_pos.p, take * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(ts.data() + at, d_ts.p, take * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(rows.data() + at * rf, d_rows.p, take * rf * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-      }
-      s0 = s1;
-    }
-    // The one key that lives in the side slot (kEmptyKey itself; the reference's map holds INT64_MIN in a
-    // bucket like any other key): handed out behind the last bucket of shard 0, as the checkpoint save
-    // writes it (it was missing from this walk, one entry fewer than size()).  A walk that is
-    // already past the shard's end (offset = the "done" value below) does not see it again.
-    bool took_special = false;
-    if (shard_idx == 0 && ids.size() < want && begin * kSlots + uint64_t(offset) <= s_end) {
-      Counters c;
-      HIP_OK(hipMemcpyAsync(&c, tb.ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      if (c.special_state == 1) {
-        const uint32_t r = c.special_row;
-        const float* src = tb.chunks[r >> tb.chunk_shift] + size_t(r & ((1u << tb.chunk_shift) - 1u)) * rf;
-        const size_t at = ids.size();
-        rows.resize((at + 1) * rf);
-        HIP_OK(hipMemcpyAsync(rows.data() + at * rf, src, rf * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        ids.push_back(kEmptyKey);
-        pos.push_back(int64_t(s_end));
-        ts.push_back(c.special_ts);
-        took_special = true;
-      }
-    }
-    // stopped on the limit: resume behind the last entry; ran off the shard's end: one bucket past it
-    // (":770 Using +1 here since end might equal to begin")
-    if (!took_special && ids.size() >= want) *new_offset = int64_t(uint64_t(pos.back()) - begin * kSlots + 1);
-    else *new_offset = int64_t((end - begin + 1) * kSlots);
-    *n_entries = int64_t(ids.size());
-    const std::vector<ckpt::SegLayout> segs = seg_layout(tb);
-    std::string all, rec;
-    std::vector<int64_t> offs(1, 0);
-    for (size_t i = 0; i < ids.size(); ++i) {
-      ckpt::encode_entry(rec, ids[i], rows.data() + i * rf, segs, int(tb.dim), ts[i]);
-      all += rec;
-      offs.push_back(int64_t(all.size()));
-    }
-    *needed = int64_t(all.size());
-    if (int64_t(offs.size()) > offsets_cap || !entry_offsets)
-      throw Error(MHTE_INVALID_ARGUMENT, "save_as_tensor: entry_offsets holds " + std::to_string(offsets_cap) +
-                                             " values, need " + std::to_string(offs.size()));
-    memcpy(entry_offsets, offs.data(), offs.size() * sizeof(int64_t));
-    if (int64_t(all.size()) > cap || (!entries && !all.empty()))
-      throw Error(MHTE_INVALID_ARGUMENT, "save_as_tensor: entries buffer too small: need " +
-                                             std::to_string(all.size()));
-    if (!all.empty()) memcpy(entries, all.data(), all.size());
+    save_as_tensor(t, table_at(t, table), shard_idx, num_shards, limit, offset, new_offset, entries, cap,
+                   entry_offsets, offsets_cap, n_entries, needed, S(stream));
   });
 }
 
 mhte_status mhte_feature_stat(const char* basename, char* names, int64_t names_cap, uint64_t* counts,
                               int32_t cap, int32_t* n_out) {
-  return guard([&] {
-    if (!basename || !*basename || !n_out) throw Error(MHTE_INVALID_ARGUMENT, "feature_stat: bad arguments");
-    const int total = discover_shards(basename);
-    std::map<std::string, uint64_t> stat;
-    for (int sh = 0; sh < total; ++sh) {
-      ckpt::RecordReader meta(ckpt::shard_name(basename, ".meta", sh, total), false);
-      std::string rec, name;
-      try {
-        while (meta.read(&rec)) {
-          uint64_t num = 0;
-          ckpt::decode_meta(reinterpret_cast<const uint8_t*>(rec.data()), rec.size(), &name, &num);
-          stat[name] += num;
-        }
-      } catch (const std::exception& e) {
-        throw Error(MHTE_INTERNAL, std::string("DataLoss: Read table metadata failed! ") + e.what());
-      }
-    }
-    *n_out = int32_t(stat.size());
-    int64_t off = 0;
-    int32_t k = 0;
-    for (auto& kv : stat) {
-      if (k >= cap || off + int64_t(kv.first.size()) + 1 > names_cap)
-        throw Error(MHTE_INVALID_ARGUMENT, "feature_stat: output buffers too small");
-      memcpy(names + off, kv.first.c_str(), kv.first.size() + 1);
-      off += int64_t(kv.first.size()) + 1;
-      counts[k++] = kv.second;
-    }
-  });
+  return guard([&] { feature_stat(basename, names, names_cap, counts, cap, n_out); });
 }
 
 // ---- multi-table pipelined step -----------------------------------------------------------------

@@ -15,6 +15,20 @@
 //                                           ERROR; <end>: stage A reports the end at that chunk
 //   readbatch <path> <snappy 0|1> <stretch bytes> <threads>  -> the same through read_batch (the
 //                                           restore path: stretches, blocks unpacked on <threads>)
+// and for the host-only parts of the checkpoint path (monolith_amd/csrc/mhte_ckpt_parts.h,
+// tests/test_ckpt_host_cpu.py; built with -DMHTE_HOST_ONLY, also under the sanitizers):
+//   shardrange <hashpower> <total>       -> "<begin> <end>" of every shard's bucket range, one per line
+//   picknshards <entries> <requested>    -> the shard count of a save
+//   stream <path> <snappy 0|1> <stretch bytes> <threads> <take>  -> the file through RecordStream,
+//                                           <take> records at a time (0: more than is left), every
+//                                           record checked against a plain RecordReader::read loop ->
+//                                           "<count> <sum of lengths> <fnv1a of lengths and bytes> <takes>
+//                                           <what three more takes return>"
+//   runs <file of int64>                 -> the ends of next_distinct_run's runs over the file's ids
+//   pool <jobs> [<failing job>...]       -> run_shard_jobs: "<indices run exactly once> <most jobs at a
+//                                           time> <jobs finished when the error arrived> <the error>"
+//   initrow <nseg> {<opt> <dim> <init> <init value> <p0> <p1>}...  -> initial_row's floats
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -22,7 +36,7 @@
 #include <thread>
 #include <vector>
 
-#include "../monolith_amd/csrc/mhte_ckpt.h"
+#include "../monolith_amd/csrc/mhte_ckpt_parts.h"
 
 using namespace mhte::ckpt;
 
@@ -221,6 +235,108 @@ int main(int argc, char** argv) {
         }
       }
       printf("%llu %u %llu %llu\n", cnt, x, total, batches);
+    } else if (cmd == "shardrange") {
+      const int total = atoi(argv[3]);
+      for (int sh = 0; sh < total; ++sh) {
+        const mhte::BucketRange r = mhte::shard_bucket_range(uint32_t(atoi(argv[2])), sh, total);
+        printf("%llu %llu\n", (unsigned long long)r.begin, (unsigned long long)r.end);
+      }
+    } else if (cmd == "picknshards") {
+      printf("%d\n", mhte::pick_nshards(atoll(argv[2]), atoi(argv[3])));
+    } else if (cmd == "stream") {
+      const bool snappy = atoi(argv[3]) != 0;
+      const uint64_t want = atoll(argv[6]) ? uint64_t(atoll(argv[6])) : ~uint64_t(0);
+      RecordReader data(argv[2], snappy);
+      ByteArena arenas[2];
+      unsigned long long cnt = 0, total = 0, takes = 0, h = 1469598103934665603ull;
+      size_t tail[3];
+      std::vector<std::string> got;
+      {
+        mhte::RecordStream in(data, arenas, size_t(atoll(argv[4])), atoi(argv[5]));
+        size_t first = 0;
+        while (const size_t k = in.take(want, &first)) {
+          ++takes;
+          for (size_t i = first; i < first + k; ++i) {
+            const RecordReader::RecRef& r = in.refs()[i];
+            data.verify(in.base() + r.off, r.len, r.crc);
+            got.emplace_back(in.base() + r.off, r.len);
+          }
+        }
+        for (size_t& t : tail) t = in.take(want, &first);
+      }
+      RecordReader plain(argv[2], snappy);
+      std::string rec;
+      for (; plain.read(&rec); ++cnt)
+        if (cnt >= got.size() || got[cnt] != rec) throw std::runtime_error("the stream differs from the read loop");
+      if (cnt != got.size()) throw std::runtime_error("the stream has more records than the read loop");
+      auto mix = [&h](unsigned char c) { h = (h ^ c) * 1099511628211ull; };
+      for (const std::string& r : got) {
+        total += r.size();
+        for (int i = 0; i < 8; ++i) mix((unsigned char)(uint64_t(r.size()) >> (8 * i)));
+        for (unsigned char c : r) mix(c);
+      }
+      printf("%llu %llu %llu %llu %zu %zu %zu\n", cnt, total, h, takes, tail[0], tail[1], tail[2]);
+    } else if (cmd == "runs") {
+      FILE* f = fopen(argv[2], "rb");
+      if (!f) throw std::runtime_error("cannot open the ids");
+      std::vector<int64_t> ids;
+      int64_t v;
+      while (fread(&v, 8, 1, f) == 1) ids.push_back(v);
+      fclose(f);
+      std::vector<uint32_t> seen;
+      for (size_t start = 0; start < ids.size();) {
+        start = mhte::next_distinct_run(ids.data(), start, ids.size(), seen);
+        printf("%zu ", start);
+      }
+      printf("\n");
+    } else if (cmd == "pool") {
+      const int n = atoi(argv[2]);
+      std::vector<std::atomic<int>> ran(static_cast<size_t>(n));
+      for (auto& r : ran) r = 0;
+      std::atomic<int> running{0}, most{0}, finished{0};
+      std::string error = "none";
+      int finished_at_error = -1;
+      try {
+        mhte::run_shard_jobs(n, [&](int i) {
+          const int now = running.fetch_add(1) + 1;
+          for (int m = most.load(); m < now && !most.compare_exchange_weak(m, now);) {
+          }
+          for (int k = 0; k < 50; ++k) std::this_thread::yield();   // (long enough for the others to start)
+          ran[size_t(i)].fetch_add(1);
+          running.fetch_sub(1);
+          finished.fetch_add(1);
+          for (int a = 3; a < argc; ++a)
+            if (atoi(argv[a]) == i) throw std::runtime_error("job " + std::to_string(i) + " failed as asked");
+        });
+      } catch (const std::exception& e) {
+        error = e.what();
+        finished_at_error = finished.load();
+      }
+      int once = 0;
+      for (auto& r : ran) once += r.load() == 1;
+      printf("%d %d %d %s\n", once, most.load(), finished_at_error, error.c_str());
+    } else if (cmd == "initrow") {
+      const int nseg = atoi(argv[2]);
+      std::vector<mhte::SegDesc> segs(size_t(nseg), mhte::SegDesc{});
+      int w = 0, st = 0;
+      for (int i = 0; i < nseg; ++i) st += atoi(argv[3 + 6 * i + 1]);
+      for (int i = 0; i < nseg; ++i) {
+        char** a = argv + 3 + 6 * i;
+        mhte::SegDesc& d = segs[size_t(i)];
+        d.opt = atoi(a[0]);
+        d.dim = atoi(a[1]);
+        d.init = atoi(a[2]);
+        d.init_value = strtof(a[3], nullptr);
+        d.init_value2 = d.init_value + 1.f;
+        d.p[0] = strtof(a[4], nullptr);
+        d.p[1] = strtof(a[5], nullptr);
+        d.w_off = w;
+        d.st_off = st;
+        w += d.dim;
+        st += mhte::opt_state_floats(d.opt, d.dim);
+      }
+      for (float x : mhte::initial_row(segs.data(), uint32_t(nseg), uint32_t(st))) printf("%.9g ", x);
+      printf("\n");
     } else {
       return 2;
     }

@@ -27,7 +27,7 @@ STATE = {SGD: (0, 0), ADAGRAD: (1, 0), FTRL: (2, 0), MOMENTUM: (1, 0), ADADELTA:
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
   exe = str(tmp_path_factory.mktemp("ckpt") / "ckpt_driver")
-  subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-o", exe,
+  subprocess.check_call(["g++", "-O2", "-std=c++17", "-DMHTE_HOST_ONLY", "-pthread", "-o", exe,
                          os.path.join(ROOT, "tests", "ckpt_host_driver.cc")])
   return exe
 
