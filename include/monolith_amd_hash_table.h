@@ -1246,6 +1246,11 @@ mhte_status mhte_shard_step_info(mhte_shard_step* s, int64_t info[4]);
  * RT/ops/multi_hash_table_update_op.cc:247-308: every shard's segments in one op) the count does not
  * depend on the world size; per 32 tables of the model. */
 mhte_status mhte_shard_step_launches(mhte_shard_step* s, int32_t out[2]);
+/* Launches of every instance of the one-launch owner update since the step was created (host-side counters, read
+ * only): out[((one float per lane ? 2 : 0) + (world > 1 ? 1 : 0)) * 3 + kind], kind 0 = the fast loop of SGD /
+ * Adagrad / FTRL tables, 1 = the generic loop (every other optimizer), 2 = the whole-segment optimizer.  Tables
+ * with an occurrence filter take the per-peer form and count nowhere here. */
+mhte_status mhte_shard_step_apply_launches(mhte_shard_step* s, int64_t out[12]);
 /* What the step's last forward + backward put on the wire through send / recv pairs (the RCCL transport and the
  * in-process group, whose device copies stand for the pairs; 0 for identity / peer stores):
  * out[0] = pairs in total, [1] = exchanges, [2] = the most pairs any one exchange took, [3] = times the HOST

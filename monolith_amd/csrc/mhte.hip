@@ -5026,6 +5026,13 @@ mhte_status mhte_shard_step_launches(mhte_shard_step* s, int32_t out[2]) {
   });
 }
 
+mhte_status mhte_shard_step_apply_launches(mhte_shard_step* s, int64_t out[12]) {
+  return guard([&] {
+    if (!s || !out) throw Error(MHTE_INVALID_ARGUMENT, "null argument");
+    for (int i = 0; i < 12; ++i) out[i] = int64_t(s->ss.apply_launches[i]);
+  });
+}
+
 mhte_status mhte_shard_step_wire_stats(mhte_shard_step* s, int64_t out[4]) {
   return guard([&] {
     if (!s || !out) throw Error(MHTE_INVALID_ARGUMENT, "null argument");

@@ -164,6 +164,9 @@ struct ShardStep {
   bool rcnt_pending = false;
   std::vector<uint32_t> est_n;  // per table: ids expected in the fullest peer block (0: not known yet)
   uint32_t launches_fwd = 0;
+  // launches of every shard_apply_kernel instance since creation (mhte_shard_step_apply_launches), indexed
+  // ((one float per lane ? 2 : 0) + (MULTI ? 1 : 0)) * 3 + (FAST ? 0 : GROUP ? 2 : 1)
+  uint64_t apply_launches[12] = {};
   uint32_t* h_flags = nullptr;  // pinned, device-visible
   uint32_t* d_flags = nullptr;
   bool alias = false;           // world == 1 without a communicator
@@ -1320,6 +1323,7 @@ struct ShardStep {
             if (k.inst3[w == 1][kd.group][kd.fast]) {
               LAUNCH_HOT(kTagShardUpsert, shard_apply_instance(w, kd.group, world > 1, kd.fast), grid, 256, st, A);
               ++launches;
+              ++apply_launches[((w == 1 ? 2 : 0) + (world > 1 ? 1 : 0)) * 3 + (kd.fast ? 0 : kd.group ? 2 : 1)];
             }
         HIP_OK(hipGetLastError());
       }

@@ -1069,6 +1069,27 @@ __device__ __forceinline__ void ipc_copy16(char* dst, const char* src, uint32_t 
   }
 }
 
+// fp16 row blocks: a table's region is cap * dim 16-bit words with cap a multiple of 4 — whole 8-byte words, at
+// an offset that is a multiple of 8 and of 16 only when (cap / 4) * dim of every table in front is even, and a
+// sender's block starts 8 bytes off for an odd rank when the block's own length is odd in 8-byte words.  So the
+// occupied part goes in 16-byte pieces where both sides are aligned for them and in 8-byte pieces otherwise, and
+// a last odd 8-byte word by itself: rounding it up to 16 bytes ran into the next table's region — for the
+// model's last table into the first four gradients of the NEXT sender's block in the peer's window.
+__device__ __forceinline__ void ipc_copy8(char* dst, const char* src, uint32_t n8, uint32_t first, uint32_t stride) {
+  const uint2* s = reinterpret_cast<const uint2*>(src);
+  uint2* d = reinterpret_cast<uint2*>(dst);
+  uint32_t done = 0;
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0u) {
+    ipc_copy16(dst, src, n8 / 2u, first, stride);
+    done = n8 & ~1u;
+  }
+  for (uint32_t i = done + first; i < n8; i += stride) {
+    const uint2 v = s[i];
+    __builtin_nontemporal_store(v.x, &d[i].x);
+    __builtin_nontemporal_store(v.y, &d[i].y);
+  }
+}
+
 __global__ __launch_bounds__(256) void shard_push_kernel(ShardPushArgs A) {
   __shared__ uint32_t ok;
   const uint32_t p = blockIdx.y;
@@ -1097,9 +1118,8 @@ __global__ __launch_bounds__(256) void shard_push_kernel(ShardPushArgs A) {
     if (!n) continue;
     if (A.ids)
       ipc_copy16(dst + size_t(tb.id_off) * 8, src + size_t(tb.id_off) * 8, (n + 1u) / 2u, first, stride);
-    else if (A.half)
-      ipc_copy16(dst + size_t(tb.row_off) * 2, src + size_t(tb.row_off) * 2, (n * tb.dim * 2u + 15u) / 16u, first,
-                 stride);
+    else if (A.half)   // (n <= cap: the rounded-up 8-byte words stay inside the table's region)
+      ipc_copy8(dst + size_t(tb.row_off) * 2, src + size_t(tb.row_off) * 2, (n * tb.dim + 3u) / 4u, first, stride);
     else
       ipc_copy16(dst + size_t(tb.row_off) * 4, src + size_t(tb.row_off) * 4, (n * tb.dim + 3u) / 4u, first, stride);
   }

@@ -69,6 +69,13 @@ def shard_block_geometry(dims, batch_per_table: int, world: int, ids_per_peer_ta
           "ids_block": (idw + 1) & ~1, "rows_block": rw}
 
 
+def _apply_launches(libmod, lib, h):
+  out = (C.c_int64 * 12)()
+  libmod.check(lib.mhte_shard_step_apply_launches(h, out))
+  return {(4 if i // 6 == 0 else 1, bool((i // 3) & 1), ("fast", "generic", "group")[i % 3]): int(out[i])
+          for i in range(12)}
+
+
 class ShardedMultiStep:
   """All tables of the model, sharded by id over the ranks, one exchange per direction for all of
   them (native_training/distributed_ps_sync.py:95-287, :289-490) — mhte_shard_step_*: the whole
@@ -252,6 +259,11 @@ class ShardedMultiStep:
     self._libmod.check(self._lib.mhte_shard_step_wire_stats(self._h, out))
     return {"pairs": int(out[0]), "exchanges": int(out[1]), "pairs_max": int(out[2]), "host_waits": int(out[3])}
 
+  def apply_launches(self):
+    """Launches of every instance of the one-launch owner update since creation (mhte_shard_step_apply_launches):
+    {(lane width 4 | 1, world > 1, "fast" | "generic" | "group"): count}."""
+    return _apply_launches(self._libmod, self._lib, self._h)
+
   def comm_ranks(self):
     """(ncclCommCount, ncclCommUserRank) of the step's own RCCL communicator; (0, 0) without one."""
     out = (C.c_int32 * 2)()
@@ -350,6 +362,10 @@ class ShardedStepGroup:
       self._libmod.check(self._lib.mhte_shard_step_launches(h, ln))
       out.append((int(ln[0]), int(ln[1])))
     return out
+
+  def apply_launches(self):
+    """Per rank: ``ShardedMultiStep.apply_launches``."""
+    return [_apply_launches(self._libmod, self._lib, h) for h in self._hs]
 
   def set_exact_order(self, on: bool = True):
     """Every rank's duplicate lists summed strictly in occurrence order (mhte_shard_step_set_exact_order)."""

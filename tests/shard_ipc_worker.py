@@ -71,20 +71,27 @@ def main():
       # the reference's standard row layout: a dim-1 FTRL bias slice in front of the vector (dims 17 / 33)
       from test_multi_step_gpu import bias_slice_specs
       specs = bias_slice_specs()
+    elif os.environ.get("MHTE_TEST_SPECS") == "fill":
+      # test_shard_forms_gpu's segment-fill model: peer blocks of 12 ids (cap / 4 odd) that the batches fill to
+      # exactly 12, 11, 1 and 0; the last table has dim 17, so a full last segment of 16-bit gradients ends 8
+      # bytes short of a 16-byte word — in front of the NEXT sender's block in the owner's window
+      from test_shard_forms_gpu import FILL_B, fill_batches, fill_specs
+      specs = fill_specs(17)
     else:
       specs = dlrm_specs(8, initial_capacity=1 << 10)   # incl. SGD and bias-FTRL + vector-Adagrad tables
+    fill = os.environ.get("MHTE_TEST_SPECS") == "fill"
     by_name = sorted(specs, key=lambda s: s.name)
-    B = 3000
+    B, cap = (FILL_B, 12) if fill else (3000, 0)
     universe = 200000 if dist_kind == "uniform" else 7000
     exact = dist_kind == "uniform"
     mt = make(specs)
     want = os.environ.get("MHTE_TEST_TRANSPORT", "ipc")    # "rccl": one DEVICE per rank (a multi-GPU node)
-    step = ShardedMultiStep(mt, B, transport=want)
+    step = ShardedMultiStep(mt, B, transport=want, ids_per_peer_table=cap)
     info = step.info()
     assert info["transport"].startswith(want), info
     if want == "rccl":
       assert step.comm_ranks() == (world, rank), (step.comm_ranks(), world, rank)
-    assert info["ids_per_peer_table"] == B, info      # whole-batch blocks: nothing can overflow
+    assert info["ids_per_peer_table"] == (cap or B), info      # whole-batch blocks: nothing can overflow
     ots = {s.name: s.oracle_table() for s in specs}   # the oracle replays EVERY rank's stream
 
     def rank_batch(s, r):
@@ -92,7 +99,10 @@ def main():
       n = B if not (r == 0 and s == 2) else 1                  # and a one-id batch
       return batch_of(specs, 100 * s + r, n, universe, dist_kind, skip)
 
-    batches = [[rank_batch(s, r) for r in range(world)] for s in range(steps + 1)]
+    if fill:
+      batches = fill_batches(specs, world, steps, cap)
+    else:
+      batches = [[rank_batch(s, r) for r in range(world)] for s in range(steps + 1)]
     rag = [ragged_of(specs, mt, batches[s][rank]) for s in range(steps + 1)]
     worst = 0.0
     for s in range(steps):

@@ -121,6 +121,22 @@ def test_processes_fp16_gradient_wire(tmp_path):
   assert all(r["ok"] for r in res)
 
 
+def test_processes_fp16_gradient_wire_bias_slice_rows(tmp_path):
+  """The fp16 wire on rows of 17 / 33 floats between processes: table regions and the odd rank's block of 16-bit
+  gradients start 8 bytes off a 16-byte boundary in the window (shard_push_kernel's 8-byte pieces)."""
+  res = run_world(2, "uniform", 4, tmp_path, {"MHTE_TEST_SPECS": "bias", "MHTE_SHARD_GRAD_FP16": "1"})
+  assert all(r["transport"].startswith("ipc") for r in res)
+
+
+def test_processes_fp16_gradient_wire_full_last_segment(tmp_path):
+  """Three processes, test_shard_forms_gpu's segment-fill model (peer blocks of 12 ids, last table of dim 17) with
+  the fp16 wire: every sender's last segment for itself is full and ends 8 bytes short of a 16-byte word.  The push
+  used to round that word up — into the first four gradients the next sender stores for the same owner."""
+  res = run_world(3, "uniform", 4, tmp_path, {"MHTE_TEST_SPECS": "fill", "MHTE_SHARD_GRAD_FP16": "1"})
+  assert len({r["pid"] for r in res}) == 3
+  assert all(r["transport"].startswith("ipc") for r in res)
+
+
 def test_coarse_window(tmp_path):
   """MHTE_SHARD_WINDOW=coarse: the windows as plain device memory (the A/B form)."""
   res = run_world(2, "uniform", 4, tmp_path, {"MHTE_SHARD_WINDOW": "coarse"})

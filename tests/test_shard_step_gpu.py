@@ -112,8 +112,11 @@ def test_group_launch_count_does_not_grow_with_the_world(world, n_tables, expect
 
 
 def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always_ahead=False, exact_order=False,
-                          universe=None, ids_per_peer_table=0, check_tables=None):
-  """check_tables(mts): called with every rank's tables after the final comparison, before the group closes."""
+                          universe=None, ids_per_peer_table=0, check_tables=None, rank_batch=None, check_group=None):
+  """check_tables(mts): called with every rank's tables after the final comparison, before the group closes;
+  check_group(grp): the same with the group.  rank_batch(step, rank) -> {table name: ids}: the caller's id
+  streams instead of the seeded ones (with dist "uniform" the caller keeps every id's occurrences in a batch
+  at or below 32; a table may be absent from a rank's batch)."""
   by_name = sorted(specs, key=lambda s: s.name)
   if universe is None:
     universe = 200000 if dist == "uniform" else 7000
@@ -127,11 +130,13 @@ def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always
   assert (info[0], info[1], info[2]) == (geo["cap"], 8 * geo["ids_block"], 4 * geo["rows_block"])
   ots = {s.name: s.oracle_table() for s in specs}
 
-  def rank_batch(step, r):
+  def seeded_batch(step, r):
     skip = (by_name[min(3, len(by_name) - 1)].name,) if (r == 1 and step % 2 == 0) else ()   # ragged: an empty table on one rank
     n = B if not (r == 0 and step == 2) else 1                 # and a one-id batch
     return batch_of(specs, 100 * step + r, n, universe, dist, skip)
 
+  if rank_batch is None:
+    rank_batch = seeded_batch
   batches = [[rank_batch(s, r) for r in range(world)] for s in range(steps + 1)]
   rag = [[ragged_of(specs, mts[r], batches[s][r]) for r in range(world)] for s in range(steps + 1)]
   pre = False
@@ -188,6 +193,8 @@ def _group_against_oracle(specs, dist, world, grad_fp16, B=3000, steps=5, always
     assert sum(sizes) == seen.size, (sp.name, sizes, seen.size)
   if check_tables is not None:
     check_tables(mts)
+  if check_group is not None:
+    check_group(grp)
   grp.close()
   return launch_counts
 
