@@ -556,6 +556,12 @@ static inline auto with_flag(bool on, F&& f) {
   return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// the instance of a retriever kernel for Table::retriever_instance()'s answer (not kRtRaw)
+template <class F>
+static inline F pick_rt(int rt, F fake_quant, F hash_net, F mixed) {
+  return rt == kRtFakeQuant ? fake_quant : (rt == kRtHashNet ? hash_net : mixed);
+}
+
 // MHTE_EXACT_ORDER in the step kernels (single-table and multi-table step alike): lists of <= kStepLightMax
 // occurrences are summed in occurrence order by the id-major groups in every mode; the heavy ones get their
 // strictly sequential sums from a launch in front of the update (`pre`: a workgroup streams a list's rows
@@ -1096,59 +1102,30 @@ struct Table {
     finish_pending(st);  // a deferred displacement pass always precedes the next op on the table
     if (n <= 0) return;
     Shape sh = pick_shape(dim, vec_ok && aligned16(out));
-    if (has_retriever) {   // the retrievers' instances, the same two launch forms as below
-      const RetrieverArgs ra = retriever_args(false, 0);
-      const int rt = retriever_instance(false);
-      if (sh.VEC == 4 && n >= 4096) {
-        const uint32_t g = uint32_t(((n + 1) / 2 * sh.G + 511) / 512);
-        TableView v = view;
-        v.trace = trace_region(kTagLookup, g, 512);
-        for_shape(sh, [&](auto g_, auto) {
-          constexpr int G = decltype(g_)::value;
-          auto fn = rt == kRtFakeQuant ? lookup_retrieve_kernel_u<G, kRtFakeQuant>
-                    : (rt == kRtHashNet ? lookup_retrieve_kernel_u<G, kRtHashNet> : lookup_retrieve_kernel_u<G, kRtMixed>);
-          LAUNCH_HOT(kTagLookup, fn, g, 512, st, v, ids, n, n_dev, out, count_hits ? 1 : 0, ra);
-        });
-        HIP_OK(hipGetLastError());
-        return;
-      }
-      const dim3 grid(uint32_t((n * sh.G + 255) / 256));
-      TableView v = view;
-      v.trace = trace_region(kTagLookup, grid.x, 256);
-      for_shape(sh, [&](auto g_, auto v_) {
-        constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
-        auto fn = rt == kRtFakeQuant ? lookup_retrieve_kernel<G, V, kRtFakeQuant>
-                  : (rt == kRtHashNet ? lookup_retrieve_kernel<G, V, kRtHashNet>
-                                      : lookup_retrieve_kernel<G, V, kRtMixed>);
-        LAUNCH_HOT(kTagLookup, fn, grid, 256, st, v, ids, n, n_dev, out, count_hits ? 1 : 0, ra);
-      });
-      HIP_OK(hipGetLastError());
-      return;
-    }
     // two ids per lane group, 512-thread workgroups, streaming stores: the fastest shape of the
     // sweep over ids per group x workgroup size x store kind (profiles/r01/f_lookup_sweep.jsonl:
-    // 6.9 us for 65 536 ids against 9.4 us for one id per group)
-    if (sh.VEC == 4 && n >= 4096) {
-      const int64_t groups = (n + 1) / 2;
-      const uint32_t g = uint32_t((groups * sh.G + 511) / 512);
-      TableView v = view;
-      v.trace = trace_region(kTagLookup, g, 512);
-      for_shape(sh, [&](auto g_, auto v_) {
-        constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
-        if constexpr (V == 4)   // (the float4 form only)
-          LAUNCH_HOT(kTagLookup, (lookup_kernel_u<G, 4, 2, 1, 512>), g, 512, st, v, ids, n, n_dev, out,
-                     count_hits ? 1 : 0);
-      });
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    const int64_t threads = n * sh.G;
-    const dim3 grid(uint32_t((threads + 255) / 256));
+    // 6.9 us for 65 536 ids against 9.4 us for one id per group); else one id per group, 256 threads
+    const bool two = sh.VEC == 4 && n >= 4096;
+    const int block = two ? 512 : 256;
+    const uint32_t grid = uint32_t(((two ? (n + 1) / 2 : n) * sh.G + block - 1) / block);
     TableView v = view;
-    v.trace = trace_region(kTagLookup, grid.x, 256);
+    v.trace = trace_region(kTagLookup, grid, block);
+    // a table with segment retrievers: the retrievers' instance of the form, their descriptors behind the
+    // raw kernel's arguments
+    const int rt = retriever_instance(false);
+    const RetrieverArgs ra = rt != kRtRaw ? retriever_args(false, 0) : RetrieverArgs{};
+    auto launch = [&](auto raw, auto retrieve) {
+      if (rt == kRtRaw) LAUNCH_HOT(kTagLookup, raw, grid, block, st, v, ids, n, n_dev, out, count_hits ? 1 : 0);
+      else LAUNCH_HOT(kTagLookup, retrieve, grid, block, st, v, ids, n, n_dev, out, count_hits ? 1 : 0, ra);
+    };
     for_shape(sh, [&](auto g_, auto v_) {
       constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
-      LAUNCH_HOT(kTagLookup, (lookup_kernel<G, V>), grid, 256, st, v, ids, n, n_dev, out, count_hits ? 1 : 0);
+      if (!two)
+        launch(lookup_kernel<G, V>, pick_rt(rt, lookup_retrieve_kernel<G, V, kRtFakeQuant>,
+                                            lookup_retrieve_kernel<G, V, kRtHashNet>, lookup_retrieve_kernel<G, V, kRtMixed>));
+      else if constexpr (V == 4)   // (the float4 form only)
+        launch(lookup_kernel_u<G, 4, 2, 1, 512>, pick_rt(rt, lookup_retrieve_kernel_u<G, kRtFakeQuant>,
+                                                         lookup_retrieve_kernel_u<G, kRtHashNet>, lookup_retrieve_kernel_u<G, kRtMixed>));
     });
     HIP_OK(hipGetLastError());
   }
@@ -1164,6 +1141,18 @@ struct Table {
   template <int G, int V, int OP>
   static auto upsert_instance(bool has_group_opt) {
     return (OP == kOpOptimize && has_group_opt) ? upsert_kernel<G, V, OP, true> : upsert_kernel<G, V, OP>;
+  }
+  // ... and both kernels' instances for retriever_instance(true): kRtHashNet (the one-segment table), else kRtMixed
+  template <int G, int V>
+  static auto upsert_backward_instance(int rt, bool has_group_opt) {
+    return rt == kRtHashNet ? upsert_backward_kernel<G, V, kRtHashNet, false>
+                            : (has_group_opt ? upsert_backward_kernel<G, V, kRtMixed, true>
+                                             : upsert_backward_kernel<G, V, kRtMixed, false>);
+  }
+  static auto slowpath_backward_fn(int vec, int rt) {
+    const bool one = rt == kRtHashNet;
+    return vec == 4 ? (one ? slowpath_backward_kernel<4, kRtHashNet> : slowpath_backward_kernel<4, kRtMixed>)
+                    : (one ? slowpath_backward_kernel<1, kRtHashNet> : slowpath_backward_kernel<1, kRtMixed>);
   }
   // the arguments every update path hands its kernels; a null lrs: zero rates
   ApplyArgs apply_args(const float* lrs, int64_t update_time, int64_t global_step, int sum_dups,
@@ -1192,31 +1181,22 @@ struct Table {
     const int64_t threads = n * sh.G;
     const dim3 grid(uint32_t((threads + 255) / 256));
     uint32_t* pend = pending.p;
-    if constexpr (OP == kOpOptimize) {
-      if (has_hash_net) {   // the retriever's Backward in front of the optimizer (Assign / AssignAdd / Reinitialize write raw)
-        const RetrieverArgs ra = retriever_args(true, a.global_step);
-        const bool one = retriever_instance(true) == kRtHashNet;
-        for_shape(sh, [&](auto g_, auto v_) {
-          constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
-          auto fn = one ? upsert_backward_kernel<G, V, kRtHashNet, false>
-                        : (has_group_opt ? upsert_backward_kernel<G, V, kRtMixed, true>
-                                         : upsert_backward_kernel<G, V, kRtMixed, false>);
-          LAUNCH_HOT(kTagUpsert, fn, grid, 256, st, view, ids, n, n_dev, values, seg_off, seg_pos, a, pend, skp, ra);
-        });
-        auto slow = sh.VEC == 4 ? (one ? slowpath_backward_kernel<4, kRtHashNet> : slowpath_backward_kernel<4, kRtMixed>)
-                                : (one ? slowpath_backward_kernel<1, kRtHashNet> : slowpath_backward_kernel<1, kRtMixed>);
-        slow<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, pend, skp, ra);
-        if (a.filter_mode) filter_maintain(st, uint64_t(n));
-        HIP_OK(hipGetLastError());
-        return;
-      }
-    }
+    // an Optimize on a table with a HashNet segment: the retriever's Backward in front of the optimizer
+    // (Assign / AssignAdd / Reinitialize write raw) — the retriever instances of both kernels, which take the
+    // descriptors and no `status`
+    const int rt = OP == kOpOptimize ? retriever_instance(true) : kRtRaw;
+    const RetrieverArgs ra = rt != kRtRaw ? retriever_args(true, a.global_step) : RetrieverArgs{};
     for_shape(sh, [&](auto g_, auto v_) {
       constexpr int G = decltype(g_)::value, V = decltype(v_)::value;
-      LAUNCH_HOT(kTagUpsert, (upsert_instance<G, V, OP>(has_group_opt)), grid, 256, st, view, ids, n, n_dev,
-                 values, seg_off, seg_pos, a, status, pend, skp);
+      if (rt == kRtRaw)
+        LAUNCH_HOT(kTagUpsert, (upsert_instance<G, V, OP>(has_group_opt)), grid, 256, st, view, ids, n, n_dev,
+                   values, seg_off, seg_pos, a, status, pend, skp);
+      else
+        LAUNCH_HOT(kTagUpsert, (upsert_backward_instance<G, V>(rt, has_group_opt)), grid, 256, st, view, ids, n, n_dev,
+                   values, seg_off, seg_pos, a, pend, skp, ra);
     });
-    slowpath_fn<OP>(sh.VEC)<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
+    if (rt == kRtRaw) slowpath_fn<OP>(sh.VEC)<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, status, pend, skp);
+    else slowpath_backward_fn(sh.VEC, rt)<<<1, 64, 0, st>>>(view, ids, values, seg_off, seg_pos, a, pend, skp, ra);
     if (a.filter_mode) filter_maintain(st, uint64_t(n));
     HIP_OK(hipGetLastError());
   }

@@ -1320,6 +1320,68 @@ __device__ __forceinline__ SlotResult upsert_resolve(const TableView& tv, Bucket
   return out;
 }
 
+// The upsert front of one lane group, the body of upsert_kernel and upsert_backward_kernel alike: probe,
+// admission filter (may drop the first occurrences of an id that is not in the table yet; an id whose occurrences
+// are all dropped is not inserted), slot (upsert_resolve), defer step (both buckets full: the slow path), row
+// update; a reinit writes status: 0 inserted, 1 existed (cuckoo_embedding_hash_table.cc:215-226), later
+// duplicates of an id always see it existing.
+// RT_ / RA_: the segment retrievers, as in lookup_role — here the retriever's Backward in the row update
+// (apply_row) of an Optimize on a table with a HashNet segment (kRtHashNet, the one-segment table; kRtMixed).
+// A macro over the kernel's own arguments and not a function like slowpath_role: behind one more level of
+// inlining the compiler allocates the raw instances' registers differently (upsert_kernel<16, 4, kOpAssign>:
+// 2955 -> 2963 instructions), and these are hot.
+#define MHTE_UPSERT_BODY(OP_, RT_, STATUS_, RA_) \
+{ \
+  const int lane = threadIdx.x & 63; \
+  const int j = lane & (G - 1); \
+  const int64_t g = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G; \
+  if (n_dev) n = min(n, int64_t(*n_dev)); \
+  bool valid = g < n; \
+  const int64_t id = valid ? ids[g] : 0; \
+  const uint64_t hv = hash_key(id); \
+  const uint64_t i1 = index_hash(tv.hp, hv); \
+  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1); \
+  Bucket* b = assume_global(tv.buckets + ((j < 4) ? i1 : i2)); \
+  int64_t k = kEmptyKey; \
+  uint32_t row = kNoRow; \
+  if (valid && id != kEmptyKey && j < 8) { \
+    k = b->key[j & 3]; \
+    row = b->row[j & 3]; \
+  } \
+  uint32_t q0 = (valid && seg_off) ? seg_off[g] : 0u; \
+  const uint32_t q1 = (valid && seg_off) ? seg_off[g + 1] : 1u; \
+  if (tv.flt_slots && a.filter_mode) { \
+    const int gbase = lane & ~(G - 1); \
+    bool contained = group_mask_of<G>(__ballot(valid && id != kEmptyKey && j < 8 && k == id), gbase) != 0; \
+    if (valid && id == kEmptyKey) contained = tv.ctr->special_state == 1; \
+    uint32_t first = 0; \
+    if (valid && j == 0) { \
+      const int mode = (a.filter_mode == 1 && a.sum_dups) ? 2 : a.filter_mode; \
+      first = filter_consult(tv, id, q1 - q0, mode, contained); \
+    } \
+    first = __shfl(first, gbase); \
+    if (first >= q1 - q0) valid = false; \
+    q0 += first; \
+  } \
+  const SlotResult sr = upsert_resolve<G>(tv, b, id, valid, k, row, lane, a.ts); \
+  if (sr.deferred && j == 0) { \
+    const uint32_t slot = atomicAdd(&tv.ctr->n_pending, 1u); \
+    pending[slot] = static_cast<uint32_t>(g); \
+    if (skip) skip[g] = q0; \
+  } \
+  if (valid && !sr.deferred) { \
+    apply_row<G, VEC, OP_, false, GROUP, RT_>(tv, row_ptr(tv, sr.r), sr.is_new, j, values, seg_off ? seg_pos : nullptr, \
+                                            q0, q1, g, a, RA_); \
+    if (OP_ == kOpReinit && j == 0) { \
+      if (seg_off) { \
+        for (uint32_t q = q0; q < q1; ++q) STATUS_[seg_pos[q]] = (q == q0 && sr.is_new) ? 0 : 1; \
+      } else { \
+        STATUS_[g] = sr.is_new ? 0 : 1; \
+      } \
+    } \
+  } \
+}
+
 template <int G, int VEC, int OP, bool GROUP = false>
 __global__ __launch_bounds__(256) void upsert_kernel(TableView tv, const int64_t* __restrict__ ids,
                                                      int64_t n, const uint32_t* __restrict__ n_dev,
@@ -1329,67 +1391,10 @@ __global__ __launch_bounds__(256) void upsert_kernel(TableView tv, const int64_t
                                                      ApplyArgs a, int32_t* __restrict__ status,
                                                      uint32_t* __restrict__ pending,
                                                      uint32_t* __restrict__ skip) {
-  const int lane = threadIdx.x & 63;
-  const int j = lane & (G - 1);
-  const int64_t g = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;
-  if (n_dev) n = min(n, int64_t(*n_dev));
-  bool valid = g < n;
-  const int64_t id = valid ? ids[g] : 0;
-  const uint64_t hv = hash_key(id);
-  const uint64_t i1 = index_hash(tv.hp, hv);
-  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1);
-
-  Bucket* b = assume_global(tv.buckets + ((j < 4) ? i1 : i2));
-  int64_t k = kEmptyKey;
-  uint32_t row = kNoRow;
-  if (valid && id != kEmptyKey && j < 8) {
-    k = b->key[j & 3];
-    row = b->row[j & 3];
-  }
-  uint32_t q0 = (valid && seg_off) ? seg_off[g] : 0u;
-  const uint32_t q1 = (valid && seg_off) ? seg_off[g + 1] : 1u;
-  // ---- admission filter: may drop the first occurrences of an id that is not in the table yet
-  if (tv.flt_slots && a.filter_mode) {
-    const int gbase = lane & ~(G - 1);
-    bool contained = group_mask_of<G>(__ballot(valid && id != kEmptyKey && j < 8 && k == id), gbase) != 0;
-    if (valid && id == kEmptyKey) contained = tv.ctr->special_state == 1;
-    uint32_t first = 0;
-    if (valid && j == 0) {
-      const int mode = (a.filter_mode == 1 && a.sum_dups) ? 2 : a.filter_mode;
-      first = filter_consult(tv, id, q1 - q0, mode, contained);
-    }
-    first = __shfl(first, gbase);
-    if (first >= q1 - q0) valid = false;  // every occurrence dropped: the id is not inserted
-    q0 += first;
-  }
-  const SlotResult sr = upsert_resolve<G>(tv, b, id, valid, k, row, lane, a.ts);
-  // ---- defer to the slow path ----
-  if (sr.deferred && j == 0) {
-    const uint32_t slot = atomicAdd(&tv.ctr->n_pending, 1u);
-    pending[slot] = static_cast<uint32_t>(g);
-    if (skip) skip[g] = q0;
-  }
-  // ---- apply ----
-  if (valid && !sr.deferred) {
-    apply_row<G, VEC, OP, false, GROUP>(tv, row_ptr(tv, sr.r), sr.is_new, j, values, seg_off ? seg_pos : nullptr,
-                          q0, q1, g, a);
-    if (OP == kOpReinit && j == 0) {
-      // status: 0 inserted, 1 existed (cuckoo_embedding_hash_table.cc:215-226); later duplicates
-      // of an id always see it existing.
-      if (seg_off) {
-        for (uint32_t q = q0; q < q1; ++q) status[seg_pos[q]] = (q == q0 && sr.is_new) ? 0 : 1;
-      } else {
-        status[g] = sr.is_new ? 0 : 1;
-      }
-    }
-  }
+  MHTE_UPSERT_BODY(OP, kRtRaw, status, nullptr)
 }
-
-// The Optimize of a table with a HashNet segment (RT: kRtHashNet, the one-segment table; kRtMixed):
-// upsert_kernel's steps, the retriever's Backward in the row update (apply_row), its descriptors a
-// kernel argument of this instance alone.
-// KEEP IN STEP with upsert_kernel: the probe, the admission filter and the defer step below are copies
-// of its own (the raw kernel's source and arguments were not to change); a change there belongs here too.
+// ... of an Optimize on a table with a HashNet segment, the retrievers' descriptors a kernel argument of this
+// instance alone
 template <int G, int VEC, int RT, bool GROUP>
 __global__ __launch_bounds__(256) void upsert_backward_kernel(TableView tv, const int64_t* __restrict__ ids,
                                                               int64_t n, const uint32_t* __restrict__ n_dev,
@@ -1398,46 +1403,7 @@ __global__ __launch_bounds__(256) void upsert_backward_kernel(TableView tv, cons
                                                               const uint32_t* __restrict__ seg_pos,
                                                               ApplyArgs a, uint32_t* __restrict__ pending,
                                                               uint32_t* __restrict__ skip, RetrieverArgs ra) {
-  const int lane = threadIdx.x & 63;
-  const int j = lane & (G - 1);
-  const int64_t g = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / G;
-  if (n_dev) n = min(n, int64_t(*n_dev));
-  bool valid = g < n;
-  const int64_t id = valid ? ids[g] : 0;
-  const uint64_t hv = hash_key(id);
-  const uint64_t i1 = index_hash(tv.hp, hv);
-  const uint64_t i2 = alt_index(tv.hp, partial_key(hv), i1);
-  Bucket* b = assume_global(tv.buckets + ((j < 4) ? i1 : i2));
-  int64_t k = kEmptyKey;
-  uint32_t row = kNoRow;
-  if (valid && id != kEmptyKey && j < 8) {
-    k = b->key[j & 3];
-    row = b->row[j & 3];
-  }
-  uint32_t q0 = (valid && seg_off) ? seg_off[g] : 0u;
-  const uint32_t q1 = (valid && seg_off) ? seg_off[g + 1] : 1u;
-  if (tv.flt_slots && a.filter_mode) {   // admission: an id whose occurrences are all dropped has no Backward
-    const int gbase = lane & ~(G - 1);
-    bool contained = group_mask_of<G>(__ballot(valid && id != kEmptyKey && j < 8 && k == id), gbase) != 0;
-    if (valid && id == kEmptyKey) contained = tv.ctr->special_state == 1;
-    uint32_t first = 0;
-    if (valid && j == 0) {
-      const int mode = (a.filter_mode == 1 && a.sum_dups) ? 2 : a.filter_mode;
-      first = filter_consult(tv, id, q1 - q0, mode, contained);
-    }
-    first = __shfl(first, gbase);
-    if (first >= q1 - q0) valid = false;
-    q0 += first;
-  }
-  const SlotResult sr = upsert_resolve<G>(tv, b, id, valid, k, row, lane, a.ts);
-  if (sr.deferred && j == 0) {
-    const uint32_t slot = atomicAdd(&tv.ctr->n_pending, 1u);
-    pending[slot] = static_cast<uint32_t>(g);
-    if (skip) skip[g] = q0;
-  }
-  if (valid && !sr.deferred)
-    apply_row<G, VEC, kOpOptimize, false, GROUP, RT>(tv, row_ptr(tv, sr.r), sr.is_new, j, values,
-                                                     seg_off ? seg_pos : nullptr, q0, q1, g, a, &ra);
+  MHTE_UPSERT_BODY(kOpOptimize, RT, ((int32_t*)nullptr), &ra)
 }
 
 // =============================================================================================

@@ -775,21 +775,19 @@ static void fused_lookup_segments(mhte_multi_table* t, const int64_t* ids, const
       gx = std::max(gx, uint32_t((uint64_t((n + 1) / 2) * g + 511) / 512));
     }
     if (gx == 0) continue;
-    bool w4 = false, w1 = false, r4 = false, r1 = false;   // raw / retriever tables per lane width
+    bool inst[2][2] = {};   // [retriever table][one float per lane]
     for (int k = 0; k < T; ++k) {
-      if (t->tables[k]->has_retriever) {
-        ((A.g[k] & 1u) ? r1 : r4) = true;
-        A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
-      } else {
-        ((A.g[k] & 1u) ? w1 : w4) = true;
-      }
+      const bool r = t->tables[k]->has_retriever;
+      inst[r][A.g[k] & 1u] = true;
+      if (r) A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
     }
-    if (w4) LAUNCH_HOT(kTagLookup, seg_lookup_kernel<4>, dim3(gx, ns), 512, st, A);
-    if (w1) LAUNCH_HOT(kTagLookup, seg_lookup_kernel<1>, dim3(gx, ns), 512, st, A);
-    if (rets && r4)
-      LAUNCH_HOT(kTagLookup, seg_lookup_retrieve_kernel<4>, dim3(gx, ns), 512, st, A, ConstRetrievers(t->d_rets.p));
-    if (rets && r1)
-      LAUNCH_HOT(kTagLookup, seg_lookup_retrieve_kernel<1>, dim3(gx, ns), 512, st, A, ConstRetrievers(t->d_rets.p));
+    const ConstRetrievers R = ConstRetrievers(t->d_rets.p);
+    for (int r = 0; r < 2; ++r)
+      for (int w = 0; w < 2; ++w) {
+        if (!inst[r][w]) continue;
+        if (r) LAUNCH_HOT(kTagLookup, (w ? seg_lookup_retrieve_kernel<1> : seg_lookup_retrieve_kernel<4>), dim3(gx, ns), 512, st, A, R);
+        else LAUNCH_HOT(kTagLookup, (w ? seg_lookup_kernel<1> : seg_lookup_kernel<4>), dim3(gx, ns), 512, st, A);
+      }
     HIP_OK(hipGetLastError());
   }
 }
@@ -854,27 +852,32 @@ static void fused_optimize_segments(mhte_multi_table* t, const int64_t* ids,
     }
     if (gx == 0) continue;
     gx = std::min<uint32_t>(gx, 1024);
-    bool inst[2][2] = {};   // [one float per lane][whole-segment optimizer]
-    bool rinst[2][2] = {};  // ... of the tables with a HashNet segment
+    bool inst[2][2][2] = {};   // [table with a HashNet segment][one float per lane][whole-segment optimizer]
     for (int k = 0; k < T; ++k) {
-      if (rets && t->tables[k]->has_hash_net) {
-        rinst[A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
-        A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
-      } else {
-        inst[A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
-      }
+      const bool r = rets && t->tables[k]->has_hash_net;
+      inst[r][A.g[k] & 1u][(A.g[k] >> 1) & 1u] = true;
+      if (r) A.g[k] |= uint8_t(kShapeRetrieverBit);   // (the raw instances pass such a table by)
     }
+    static void (*const kRaw[2][2])(SegUpsertArgs) = {{seg_upsert_kernel<4, false>, seg_upsert_kernel<4, true>},
+                                                      {seg_upsert_kernel<1, false>, seg_upsert_kernel<1, true>}};
+    static void (*const kBackward[2][2])(SegUpsertArgs, ConstRetrievers) = {
+        {seg_upsert_backward_kernel<4, false>, seg_upsert_backward_kernel<4, true>},
+        {seg_upsert_backward_kernel<1, false>, seg_upsert_backward_kernel<1, true>}};
     const ConstRetrievers R = ConstRetrievers(t->d_rets.p);
-    if (rinst[0][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<4, false>), dim3(gx, ns), 256, st, A, R);
-    if (rinst[1][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<1, false>), dim3(gx, ns), 256, st, A, R);
-    if (rinst[0][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<4, true>), dim3(gx, ns), 256, st, A, R);
-    if (rinst[1][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_backward_kernel<1, true>), dim3(gx, ns), 256, st, A, R);
-    if (rinst[0][0] || rinst[1][0] || rinst[0][1] || rinst[1][1]) seg_slow_backward_kernel<<<T, 64, 0, st>>>(A, R);
-    if (inst[0][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<4, false>), dim3(gx, ns), 256, st, A);
-    if (inst[1][0]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<1, false>), dim3(gx, ns), 256, st, A);
-    if (inst[0][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<4, true>), dim3(gx, ns), 256, st, A);
-    if (inst[1][1]) LAUNCH_HOT(kTagUpsert, (seg_upsert_kernel<1, true>), dim3(gx, ns), 256, st, A);
-    seg_slow_kernel<<<T, 64, 0, st>>>(A);
+    // the retriever tables first, displacement pass included: it leaves such a table's pending list empty, so
+    // the raw pass — which runs for every table — finds nothing to do there
+    for (int r = 1; r >= 0; --r) {
+      bool any = false;
+      for (int grp = 0; grp < 2; ++grp)
+        for (int w = 0; w < 2; ++w) {
+          if (!inst[r][w][grp]) continue;
+          any = true;
+          if (r) LAUNCH_HOT(kTagUpsert, kBackward[w][grp], dim3(gx, ns), 256, st, A, R);
+          else LAUNCH_HOT(kTagUpsert, kRaw[w][grp], dim3(gx, ns), 256, st, A);
+        }
+      if (r && any) seg_slow_backward_kernel<<<T, 64, 0, st>>>(A, R);
+      if (!r) seg_slow_kernel<<<T, 64, 0, st>>>(A);
+    }
     HIP_OK(hipGetLastError());
     for (int k = 0; k < T; ++k)
       if (per_table[size_t(k)]) ++t->tables[k]->mut_epoch;

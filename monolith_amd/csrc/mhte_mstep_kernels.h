@@ -608,64 +608,59 @@ struct SegLookupArgs {
 };
 static_assert(sizeof(SegLookupArgs) <= 4096, "kernel arguments exceed 4 KB");
 
-template <int G, int VEC = 4>
-__device__ __forceinline__ void seg_lookup_loop(const TableView& tv, const int64_t* ids, int64_t n,
-                                                float* out, int count_hits) {
-  const int64_t ngroups = (n + 1) / 2;
-#pragma unroll 1
-  for (int64_t g = (int64_t(blockIdx.x) * 512 + threadIdx.x) / G; g < ngroups;
-       g += int64_t(gridDim.x) * 512 / G)
-    lookup_role_u<G, VEC, 2, 1>(tv, ids, n, nullptr, out, count_hits, g);
-}
-
-template <int VW>
-__global__ __launch_bounds__(512) void seg_lookup_kernel(SegLookupArgs A) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t n = A.id_off[y + 1] - A.id_off[y];
-  if (n == 0) return;
-  const uint32_t t = (A.seg0 + y) % A.T;
-  if (!MHTE_SHAPE_IS(VW, A.g[t])) return;
-  const TableView& tv = deref_const(A.views + t);
-  const int64_t* ids = A.ids + A.id_off[y];
-  float* out = A.out + size_t(A.emb_off[y]);
-  const int ch = A.count_hits[t];
-#define MHTE_SEGL_CALL(G_, V_) seg_lookup_loop<G_, V_>(tv, ids, n, out, ch)
-  MHTE_SWITCH_G(VW, A.g[t], MHTE_SEGL_CALL)
-#undef MHTE_SEGL_CALL
-}
-
 // The segments of tables with segment retrievers (mhte_qat_kernels.h): their shape code carries
 // kShapeRetrieverBit, which no case of MHTE_SWITCH_G matches — the raw instances leave such a table's
-// workgroups at once — and these instances serve them, the retrievers' descriptors (one per table, device
-// memory) a kernel argument of their own.  The per-column form (kRtMixed) for every such table.
+// workgroups at once — and the retriever instances serve them, the retrievers' descriptors (one per table,
+// device memory) a kernel argument of their own.  The per-column form (kRtMixed) for every such table.
+// A raw and a retriever kernel below differ in the tables they accept, that argument and RT, nothing else.
 constexpr uint32_t kShapeRetrieverBit = 4u;
 typedef const MHTE_CONST RetrieverArgs* ConstRetrievers;
 
-template <int G, int VEC = 4>
-__device__ __forceinline__ void seg_lookup_retrieve_loop(const TableView& tv, const int64_t* ids, int64_t n,
-                                                         float* out, int count_hits, const RetrieverArgs& ra) {
+// A workgroup's segment y = blockIdx.y of a launch (A: SegLookupArgs / SegUpsertArgs): its n ids start at
+// A.id_off[y] and belong to table t; the workgroup leaves where the segment is empty or the instance (VW, RT_)
+// does not serve a table of t's shape code.  (Macros over the kernel's own scope, here and below, and not one
+// more function around the loops: behind another level of inlining the compiler allocates the raw instances'
+// registers differently — seg_upsert_kernel<4, false> went over its 128 VGPRs and spilled.)
+#define MHTE_SEG_DECODE(RT_)                                            \
+  const uint32_t y = blockIdx.y;                                        \
+  const uint32_t n = A.id_off[y + 1] - A.id_off[y];                     \
+  if (n == 0) return;                                                   \
+  const uint32_t t = (A.seg0 + y) % A.T;                                \
+  if (RT_ != kRtRaw && !(A.g[t] & kShapeRetrieverBit)) return;          \
+  if (!MHTE_SHAPE_IS(VW, A.g[t])) return;
+template <int RT>
+constexpr uint32_t kSegRetrieverBit = RT != kRtRaw ? kShapeRetrieverBit : 0u;
+
+template <int G, int VEC = 4, int RT = kRtRaw>
+__device__ __forceinline__ void seg_lookup_loop(const TableView& tv, const int64_t* ids, int64_t n,
+                                                float* out, int count_hits, const RetrieverArgs* ra = nullptr) {
   const int64_t ngroups = (n + 1) / 2;
 #pragma unroll 1
   for (int64_t g = (int64_t(blockIdx.x) * 512 + threadIdx.x) / G; g < ngroups;
        g += int64_t(gridDim.x) * 512 / G)
-    lookup_role_u<G, VEC, 2, 1, kRtMixed>(tv, ids, n, nullptr, out, count_hits, g, nullptr, &ra);
+    lookup_role_u<G, VEC, 2, 1, RT>(tv, ids, n, nullptr, out, count_hits, g, nullptr, ra);
 }
 
+// RA_: the declaration of table t's descriptors `ra` (retriever instances)
+#define MHTE_SEG_LOOKUP_BODY(RT_, RA_)                                  \
+  MHTE_SEG_DECODE(RT_)                                                  \
+  const TableView& tv = deref_const(A.views + t);                       \
+  RA_                                                                   \
+  const int64_t* ids = A.ids + A.id_off[y];                             \
+  float* out = A.out + size_t(A.emb_off[y]);                            \
+  const int ch = A.count_hits[t];                                       \
+  MHTE_SWITCH_G(VW, A.g[t] & ~kSegRetrieverBit<RT_>, MHTE_SEGL_CALL)
+template <int VW>
+__global__ __launch_bounds__(512) void seg_lookup_kernel(SegLookupArgs A) {
+#define MHTE_SEGL_CALL(G_, V_) seg_lookup_loop<G_, V_>(tv, ids, n, out, ch)
+  MHTE_SEG_LOOKUP_BODY(kRtRaw, )
+#undef MHTE_SEGL_CALL
+}
 template <int VW>
 __global__ __launch_bounds__(512) void seg_lookup_retrieve_kernel(SegLookupArgs A, ConstRetrievers rets) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t n = A.id_off[y + 1] - A.id_off[y];
-  if (n == 0) return;
-  const uint32_t t = (A.seg0 + y) % A.T;
-  if (!(A.g[t] & kShapeRetrieverBit) || !MHTE_SHAPE_IS(VW, A.g[t])) return;
-  const TableView& tv = deref_const(A.views + t);
-  const RetrieverArgs ra = deref_const(rets + t);
-  const int64_t* ids = A.ids + A.id_off[y];
-  float* out = A.out + size_t(A.emb_off[y]);
-  const int ch = A.count_hits[t];
-#define MHTE_SEGLR_CALL(G_, V_) seg_lookup_retrieve_loop<G_, V_>(tv, ids, n, out, ch, ra)
-  MHTE_SWITCH_G(VW, A.g[t] & ~kShapeRetrieverBit, MHTE_SEGLR_CALL)
-#undef MHTE_SEGLR_CALL
+#define MHTE_SEGL_CALL(G_, V_) seg_lookup_loop<G_, V_, kRtMixed>(tv, ids, n, out, ch, &ra)
+  MHTE_SEG_LOOKUP_BODY(kRtMixed, const RetrieverArgs ra = deref_const(rets + t);)
+#undef MHTE_SEGL_CALL
 }
 
 // FusedOptimize on ids that are distinct within every segment (they come out of
@@ -689,10 +684,12 @@ struct SegUpsertArgs {
 };
 static_assert(sizeof(SegUpsertArgs) <= 4096, "kernel arguments exceed 4 KB");
 
-template <int G, int VEC = 4, bool GROUP = false>
+// RT / ra: the retriever's Backward in the row update (tables with a HashNet segment), as in MHTE_UPSERT_BODY
+template <int G, int VEC = 4, bool GROUP = false, int RT = kRtRaw>
 __device__ __forceinline__ void seg_upsert_loop(const TableView& tv, const int64_t* ids, uint32_t n,
                                                 const float* values, const ApplyArgs& a,
-                                                uint32_t* pending, uint32_t id_base, uint32_t seg) {
+                                                uint32_t* pending, uint32_t id_base, uint32_t seg,
+                                                const RetrieverArgs* ra = nullptr) {
   const int lane = threadIdx.x & 63;
   const int j = lane & (G - 1);
   const uint32_t ngroups_wg = 256 / G;
@@ -720,11 +717,20 @@ __device__ __forceinline__ void seg_upsert_loop(const TableView& tv, const int64
       pending[2 * slot + 1] = seg;
     }
     if (valid && !sr.deferred)
-      apply_row<G, VEC, kOpOptimize, false, GROUP>(tv, row_ptr(tv, sr.r), sr.is_new, j, values, nullptr,
-                                                   0u, 1u, int64_t(g), a);
+      apply_row<G, VEC, kOpOptimize, false, GROUP, RT>(tv, row_ptr(tv, sr.r), sr.is_new, j, values, nullptr,
+                                                       0u, 1u, int64_t(g), a, ra);
   }
 }
 
+#define MHTE_SEG_UPSERT_BODY(RT_, RA_)                                  \
+  MHTE_SEG_DECODE(RT_)                                                  \
+  if (((A.g[t] & kShapeGroupBit) != 0u) != GROUP) return;               \
+  const TableView& tv = deref_const(A.views + t);                       \
+  RA_                                                                   \
+  const int64_t* ids = A.ids + A.id_off[y];                             \
+  const float* values = A.grads + size_t(A.grad_off[y]);                \
+  uint32_t* pend = A.pending[t];                                        \
+  MHTE_SWITCH_G(VW, A.g[t] & ~(kShapeGroupBit | kSegRetrieverBit<RT_>), MHTE_SEGU_CALL)
 // (four workgroups per CU = 128 VGPRs, which the loop fits without a spill; left to itself the
 // compiler takes 132 and the owner's upsert of the sharded step runs 17 us instead of 13.8)
 #ifndef MHTE_SEGU_OCC
@@ -732,128 +738,58 @@ __device__ __forceinline__ void seg_upsert_loop(const TableView& tv, const int64
 #endif
 template <int VW, bool GROUP = false>
 __global__ __launch_bounds__(256, GROUP ? 1 : MHTE_SEGU_OCC) void seg_upsert_kernel(SegUpsertArgs A) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t n = A.id_off[y + 1] - A.id_off[y];
-  if (n == 0) return;
-  const uint32_t t = (A.seg0 + y) % A.T;
-  if (!MHTE_SHAPE_IS(VW, A.g[t]) || ((A.g[t] & kShapeGroupBit) != 0u) != GROUP) return;
-  const TableView& tv = deref_const(A.views + t);
-  const int64_t* ids = A.ids + A.id_off[y];
-  const float* values = A.grads + size_t(A.grad_off[y]);
-  uint32_t* pend = A.pending[t];
 #define MHTE_SEGU_CALL(G_, V_) seg_upsert_loop<G_, V_, GROUP>(tv, ids, n, values, A.a[t], pend, A.id_off[y], y)
-  MHTE_SWITCH_G(VW, A.g[t] & ~kShapeGroupBit, MHTE_SEGU_CALL)
+  MHTE_SEG_UPSERT_BODY(kRtRaw, )
+#undef MHTE_SEGU_CALL
+}
+template <int VW, bool GROUP>
+__global__ __launch_bounds__(256) void seg_upsert_backward_kernel(SegUpsertArgs A, ConstRetrievers rets) {
+#define MHTE_SEGU_CALL(G_, V_) \
+  seg_upsert_loop<G_, V_, GROUP, kRtMixed>(tv, ids, n, values, A.a[t], pend, A.id_off[y], y, &ra)
+  MHTE_SEG_UPSERT_BODY(kRtMixed, const RetrieverArgs ra = deref_const(rets + t);)
 #undef MHTE_SEGU_CALL
 }
 
-// ... of tables with a HashNet segment: seg_upsert_loop's steps (KEEP IN STEP with it), the retriever's Backward
-// in the row update
-template <int G, int VEC, bool GROUP>
-__device__ __forceinline__ void seg_upsert_backward_loop(const TableView& tv, const int64_t* ids, uint32_t n,
-                                                         const float* values, const ApplyArgs& a,
-                                                         uint32_t* pending, uint32_t id_base, uint32_t seg,
-                                                         const RetrieverArgs& ra) {
-  const int lane = threadIdx.x & 63;
-  const int j = lane & (G - 1);
-  const uint32_t ngroups_wg = 256 / G;
-#pragma unroll 1
-  for (uint32_t g0 = blockIdx.x * ngroups_wg; g0 < n; g0 += gridDim.x * ngroups_wg) {  // wave-uniform
-    const uint32_t g = g0 + threadIdx.x / G;
-    bool valid = g < n;
-    const int64_t id = valid ? ids[g] : 0;
-    Probe<G> pr = probe_issue<G>(tv, id, valid, j);
-    if (tv.flt_slots && a.filter_mode) {
-      const int gbase = lane & ~(G - 1);
-      bool contained = group_mask_of<G>(__ballot(valid && id != kEmptyKey && j < 8 && pr.k == id), gbase) != 0;
-      if (valid && id == kEmptyKey) contained = tv.ctr->special_state == 1;
-      uint32_t first = 0;
-      if (valid && j == 0) first = filter_consult(tv, id, 1u, 1, contained);
-      if (__shfl(first, gbase) != 0u) valid = false;
-    }
-    const SlotResult sr = upsert_resolve<G>(tv, (Bucket*)pr.b, id, valid, pr.k, pr.row, lane, a.ts);
-    if (sr.deferred && j == 0) {
-      const uint32_t slot = atomicAdd(&tv.ctr->n_pending, 1u);
-      pending[2 * slot] = id_base + g;
-      pending[2 * slot + 1] = seg;
-    }
-    if (valid && !sr.deferred)
-      apply_row<G, VEC, kOpOptimize, false, GROUP, kRtMixed>(tv, row_ptr(tv, sr.r), sr.is_new, j, values, nullptr,
-                                                             0u, 1u, int64_t(g), a, &ra);
-  }
-}
-
-template <int VW, bool GROUP>
-__global__ __launch_bounds__(256) void seg_upsert_backward_kernel(SegUpsertArgs A, ConstRetrievers rets) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t n = A.id_off[y + 1] - A.id_off[y];
-  if (n == 0) return;
-  const uint32_t t = (A.seg0 + y) % A.T;
-  if (!(A.g[t] & kShapeRetrieverBit) || !MHTE_SHAPE_IS(VW, A.g[t]) || ((A.g[t] & kShapeGroupBit) != 0u) != GROUP)
-    return;
-  const TableView& tv = deref_const(A.views + t);
-  const RetrieverArgs ra = deref_const(rets + t);
-  const int64_t* ids = A.ids + A.id_off[y];
-  const float* values = A.grads + size_t(A.grad_off[y]);
-  uint32_t* pend = A.pending[t];
-#define MHTE_SEGUB_CALL(G_, V_) \
-  seg_upsert_backward_loop<G_, V_, GROUP>(tv, ids, n, values, A.a[t], pend, A.id_off[y], y, ra)
-  MHTE_SWITCH_G(VW, A.g[t] & ~(kShapeGroupBit | kShapeRetrieverBit), MHTE_SEGUB_CALL)
-#undef MHTE_SEGUB_CALL
-}
-
-// ... and their displacement pass, launched in front of seg_slow_kernel: it leaves such a table's pending list
-// empty (slow_pass_done), so the raw pass that follows finds nothing to do there
-__global__ __launch_bounds__(64) void seg_slow_backward_kernel(SegUpsertArgs A, ConstRetrievers rets) {
-  __shared__ BfsSlot q[kMaxCuckooCount];
-  __shared__ CuckooRecord path[kMaxBfsPathLen];
-  const uint32_t t = blockIdx.x;
-  if (!(A.g[t] & kShapeRetrieverBit)) return;
-  const TableView& tv = deref_const(A.views + t);
-  const RetrieverArgs ra = deref_const(rets + t);
-  const int lane = threadIdx.x;
-  const uint32_t np = tv.ctr->n_pending;
-  if (np == 0) return;
-  const uint32_t* pending = A.pending[t];
-  const ApplyArgs& a = A.a[t];
-  for (uint32_t i = 0; i < np; ++i) {
-    const uint32_t gp = pending[2 * i], seg = pending[2 * i + 1];
-    const SlowPlaced pl = slow_place(tv, A.ids[gp], a, q, path, lane);
-    if (pl.ok) {
-      const float* values = A.grads + size_t(A.grad_off[seg]);
-      const int64_t index = int64_t(gp - A.id_off[seg]);
-      if (A.g[t] & 1u)
-        apply_row<64, 1, kOpOptimize, false, true, kRtMixed>(tv, row_ptr(tv, pl.r), true, lane, values, nullptr, 0u,
-                                                             1u, index, a, &ra);
-      else
-        apply_row<64, 4, kOpOptimize, false, true, kRtMixed>(tv, row_ptr(tv, pl.r), true, lane, values, nullptr, 0u,
-                                                             1u, index, a, &ra);
-    }
-    __syncthreads();
-  }
+// displacement pass of a fused optimize, one wavefront per table: slow_place / the 64-lane update /
+// slow_pass_done (mhte_kernels.h) over the table's pending list, one entry per id.  The last argument: the update
+// of the placed row pl.r from entry (gp, seg)'s gradient row.
+#define MHTE_SEG_SLOW_BODY(RT_, RA_, ...)                                            \
+  __shared__ BfsSlot q[kMaxCuckooCount];                                             \
+  __shared__ CuckooRecord path[kMaxBfsPathLen];                                      \
+  const uint32_t t = blockIdx.x;                                                     \
+  if (RT_ != kRtRaw && !(A.g[t] & kShapeRetrieverBit)) return;                       \
+  const TableView& tv = deref_const(A.views + t);                                    \
+  RA_                                                                                \
+  const int lane = threadIdx.x;                                                      \
+  const uint32_t np = tv.ctr->n_pending;                                             \
+  if (np == 0) return;                                                               \
+  const uint32_t* pending = A.pending[t];                                            \
+  const ApplyArgs& a = A.a[t];                                                       \
+  for (uint32_t i = 0; i < np; ++i) {                                                \
+    const uint32_t gp = pending[2 * i], seg = pending[2 * i + 1];                    \
+    const SlowPlaced pl = slow_place(tv, A.ids[gp], a, q, path, lane);               \
+    if (pl.ok) {                                                                     \
+      __VA_ARGS__;                                                                   \
+    }                                                                                \
+    __syncthreads();                                                                 \
+  }                                                                                  \
   slow_pass_done<false>(tv, lane);
-}
-
-// displacement pass of a fused optimize, one wavefront per table: slow_place / apply_row_wave /
-// slow_pass_done (mhte_kernels.h) over the table's pending list, one entry per id
 __global__ __launch_bounds__(64) void seg_slow_kernel(SegUpsertArgs A) {
-  __shared__ BfsSlot q[kMaxCuckooCount];
-  __shared__ CuckooRecord path[kMaxBfsPathLen];
-  const uint32_t t = blockIdx.x;
-  const TableView& tv = deref_const(A.views + t);
-  const int lane = threadIdx.x;
-  const uint32_t np = tv.ctr->n_pending;
-  if (np == 0) return;
-  const uint32_t* pending = A.pending[t];
-  const ApplyArgs& a = A.a[t];
-  for (uint32_t i = 0; i < np; ++i) {
-    const uint32_t gp = pending[2 * i], seg = pending[2 * i + 1];
-    const SlowPlaced pl = slow_place(tv, A.ids[gp], a, q, path, lane);
-    if (pl.ok)
-      apply_row_wave<kOpOptimize, false>(tv, A.g[t], row_ptr(tv, pl.r), true, lane, A.grads + size_t(A.grad_off[seg]),
-                                         int64_t(gp - A.id_off[seg]), a);
-    __syncthreads();
-  }
-  slow_pass_done<false>(tv, lane);
+  MHTE_SEG_SLOW_BODY(kRtRaw, ,
+                     apply_row_wave<kOpOptimize, false>(tv, A.g[t], row_ptr(tv, pl.r), true, lane,
+                                                        A.grads + size_t(A.grad_off[seg]), int64_t(gp - A.id_off[seg]), a))
+}
+// ... of the tables with a HashNet segment, launched in front of seg_slow_kernel: it leaves such a table's
+// pending list empty (slow_pass_done), so the raw pass that follows finds nothing to do there.  The update:
+// the GROUP form with the retriever's Backward, VEC from bit 0 of the shape code.
+__global__ __launch_bounds__(64) void seg_slow_backward_kernel(SegUpsertArgs A, ConstRetrievers rets) {
+#define MHTE_SEGS_APPLY(V_) \
+  apply_row<64, V_, kOpOptimize, false, true, kRtMixed>(tv, row_ptr(tv, pl.r), true, lane, values, nullptr, 0u, 1u, index, a, &ra)
+  MHTE_SEG_SLOW_BODY(kRtMixed, const RetrieverArgs ra = deref_const(rets + t);,
+                     const float* values = A.grads + size_t(A.grad_off[seg]);
+                     const int64_t index = int64_t(gp - A.id_off[seg]);
+                     if (A.g[t] & 1u) MHTE_SEGS_APPLY(1); else MHTE_SEGS_APPLY(4))
+#undef MHTE_SEGS_APPLY
 }
 
 }  // namespace mhte

@@ -730,3 +730,145 @@ def test_serialized_comp_config_fields_reach_the_retriever():
         _lib.check(t._lib.mhte_table_set_retriever(t.handle, 0, 0, _lib.MHTE_RETRIEVER_HASH_NET, arr, 4))   # pylint: disable=protected-access
       finally:
         t.close()
+
+
+# =========================================================================== 14. HashNet rows behind the displacement pass
+DISP_CAP, DISP_HP, DISP_N, DISP_SEED = 1 << 10, 8, 920, 3
+
+
+def _ids_with_full_home_buckets(ids, cap, hp):
+  """positions of the ids that find both home buckets full when they arrive one by one: the oracle's table of
+  the same capacity, its bucket occupancy read before every insert (a condition on the inputs)"""
+  L = O.lib()
+  ot = O.Table(O.segment(1, O.OPT_SGD), cap)
+  full = []
+  for k, i in enumerate(ids):
+    _, pos, _, _ = ot.dump(with_rows=False)
+    occ = np.bincount(pos >> 2, minlength=1 << hp)
+    hv = L.mo_hash(int(i))
+    i1 = hv & ((1 << hp) - 1)
+    i2 = L.mo_alt_index(hp, L.mo_partial(hv), i1)
+    if occ[i1] == 4 and occ[i2] == 4:
+      full.append(k)
+    ot.assign([i], np.zeros((1, 1), np.float32))
+  assert ot.hashpower() == hp and ot.size() == len(ids)
+  return full
+
+
+def test_hash_net_rows_placed_by_the_displacement_pass():
+  """920 distinct new ids into a table pre-sized to 1024 slots (max_load_factor 0.95, the recipe of
+  test_slow_path_displacement_at_high_load), 128 per call: ids whose two buckets are full go through the
+  displacement pass of the retriever tables (slowpath_backward_kernel; seg_slow_backward_kernel on the
+  one-launch fused optimize), which applies the same first update as the fast path: every id is new and seen
+  once, so its row is 0.5 - lr * Backward(0.5, g, global_step).  Tolerance and its reasoning: as in
+  test_hash_net_update_matches_the_oracle_on_every_route (|grad| <= 1, lr 0.1, scale <= 2.45).  The routes are
+  that test's three and the fused optimize with ids_unique_per_segment, the only one that reaches the segment
+  kernels."""
+  from tests.test_parity_gpu import _check_placement_valid
+  dim, amp, lr = 8, 0.1, 0.1
+  rng = np.random.default_rng(DISP_SEED)
+  ids = rng.integers(1, 2**60, DISP_N)
+  assert np.unique(ids).size == DISP_N
+  g = rng.uniform(-1, 1, size=(DISP_N, dim)).astype(np.float32)
+  full = _ids_with_full_home_buckets(ids, DISP_CAP, DISP_HP)
+  print("ids with both home buckets full at their insertion: %d of %d" % (len(full), DISP_N))
+  assert len(full) >= 8          # (every route runs all the ids, so each has them all)
+  calls = [(lo, min(lo + 128, DISP_N), STEPS[min(k, len(STEPS) - 1)]) for k, lo in enumerate(range(0, DISP_N, 128))]
+  hn = Q.HashNet(step_size=200, amplitude=amp)
+  exp = np.empty((DISP_N, dim), np.float64)
+  for lo, hi, gs in calls:
+    exp[lo:hi] = 0.5 - lr * hn.backward(np.full((hi - lo, dim), 0.5, np.float32), g[lo:hi], gs)
+  lrs = np.array([lr], np.float32)
+  for route in ("apply_gradients", "fused_apply_gradient", "fused_unique", "table_optimize_n"):
+    mt = make({"t": entry.make_table_config(
+        [seg(dim, opt=entry.SgdOptimizer(lr), comp=entry.OneBitCompressor(step_size=200, amplitude=amp),
+             init=entry.ConstantsInitializer(0.5))],
+        entry.CuckooHashTableConfig(initial_capacity=DISP_CAP, max_load_factor=0.95))})
+    for s, (lo, hi, gs) in enumerate(calls):
+      b, gt = ids_t(ids[lo:hi]), val_t(g[lo:hi])
+      n, n0 = hi - lo, (hi - lo) // 2
+      if route == "apply_gradients":
+        mt.apply_gradients({"t": (b, gt)}, global_step=gs, req_time=100 + s)
+      elif route.startswith("fused"):
+        mt.fused_apply_gradient(b, None, np.array([n0, n - n0], np.int32), gt.reshape(-1),
+                                np.array([0, n0, n], np.int32), np.array([0, n0 * dim, n * dim], np.int32),
+                                gs, 100 + s, 2, ids_unique_per_segment=route == "fused_unique")
+      else:
+        mt.table_optimize_n("t", b, None, gt, lrs, 100 + s, global_step=gs, flags=0)
+    st = mt.stats("t")
+    assert st.dropped == 0 and st.hashpower == DISP_HP, route
+    assert mt.size("t") == DISP_N, route
+    assert mt.hash_net_scale("t", 0) == pytest.approx(hn.scale, rel=1e-6)
+    got = stored_weights(mt, "t", ids)[:, :dim]
+    diff = np.abs(got.astype(np.float64) - exp)
+    print("displacement %s: max |row - truth| = %.3e, over the ids with full home buckets %.3e" %
+          (route, diff.max(), diff[full].max()))
+    np.testing.assert_allclose(got, exp, rtol=0, atol=1e-5, err_msg=route)
+    _check_placement_valid(mt, "t", DISP_HP)
+    mt.close()
+
+
+# =========================================================================== 15. partial admission
+def test_hash_net_table_admits_part_of_an_ids_occurrences():
+  """Occurrence threshold 3 on a HashNet table, one optimizer step per occurrence (flags = 0): of a new id's five
+  occurrences in one call the filter drops the first three and the update applies the last two; an id seen
+  twice stays out, and the next call drops its third sighting and applies its fourth.  Which occurrences pass:
+  oracle.SlidingFilter asked once per occurrence of an id the table does not hold (the checker of
+  tests/test_boundary_gpu.py); those, in order, as Backward + SGD from 0.5 are the truth, to 1e-5 as above.
+  Then the same occurrences as five segments of distinct ids through fused_apply_gradient (one consultation
+  with count 1 per segment and id)."""
+  dim, amp, lr, thr = 8, 0.1, 0.1, 3
+  new = np.arange(1, 5, dtype=np.int64) << 17    # (distinct 12-bit filter signatures: no two ids share a count)
+  segs = [list(new[:3]) + ([new[3]] if s in (1, 3) else []) for s in range(5)]
+  b = np.array([i for sg in segs for i in sg], np.int64)       # a, b, c five times; d twice
+  rng = np.random.default_rng(15)
+  calls = [(b, rng.uniform(-1, 1, size=(b.size, dim)).astype(np.float32), gs) for gs in (200, 400)]
+  model = O.SlidingFilter(1000, 7, defer_advance=True)         # (HashFilter's default split_num)
+  hn = Q.HashNet(step_size=200, amplitude=amp)
+  rows, applied, after = {}, [], []
+  for ids, g, gs in calls:
+    n_app = 0
+    for i, gi in zip(ids, g):
+      i = int(i)
+      if i not in rows:
+        if model.should_be_filtered(i, 1, thr):
+          continue
+        rows[i] = np.full(dim, 0.5, np.float64)
+      w32 = rows[i].astype(np.float32)
+      rows[i] = (w32 - np.float32(lr) * hn.backward(w32, gi, gs).astype(np.float32)).astype(np.float64)
+      n_app += 1
+    model.advance_if_full()
+    applied.append(n_app)
+    after.append(({k: v.copy() for k, v in rows.items()}, [model.get(int(i)) for i in new], float(hn.scale)))
+  # the case is the one meant: 3 x 2 of 17 occurrences in the first call (d absent), 3 x 5 + 1 in the second
+  assert applied == [6, 16] and sorted(after[0][0]) == [int(i) for i in new[:3]]
+  lrs = np.array([lr], np.float32)
+  offs = np.concatenate([[0], np.cumsum([len(sg) for sg in segs])]).astype(np.int32)
+  for route in ("table_optimize_n", "fused_apply_gradient"):
+    flt = HashFilter(capacity=1000)
+    cfg = cfg_of([seg(dim, opt=entry.SgdOptimizer(lr), comp=entry.OneBitCompressor(step_size=200, amplitude=amp),
+                      init=entry.ConstantsInitializer(0.5))],
+                 slot_occurrence_threshold_config=entry.SlotOccurrenceThresholdConfig(thr, {}))
+    mt = make({"t": cfg}, hash_filter=flt)
+    for s, (ids, g, gs) in enumerate(calls):
+      gt = val_t(g)
+      keep = gt.clone()
+      if route == "table_optimize_n":
+        mt.table_optimize_n("t", ids_t(ids), None, gt, lrs, 100 + s, global_step=gs, flags=0)
+      else:
+        mt.fused_apply_gradient(ids_t(ids), None, np.diff(offs).astype(np.int32), gt.reshape(-1), offs,
+                                (offs * dim).astype(np.int32), gs, 100 + s, 5, ids_unique_per_segment=True)
+      assert torch.equal(gt, keep), (route, s)
+      exp_rows, exp_counts, exp_scale = after[s]
+      present = mt.contains("t", ids_t(new)).cpu().tolist()
+      assert present == [int(i) in exp_rows for i in new], (route, s)
+      assert mt.size("t") == len(exp_rows), (route, s)
+      np.testing.assert_array_equal(flt.get(ids_t(new)).cpu().numpy(), exp_counts, err_msg="%s call %d" % (route, s))
+      assert mt.hash_net_scale("t", 0) == pytest.approx(exp_scale, rel=1e-6), (route, s)
+      held = np.array(sorted(exp_rows), np.int64)
+      got = stored_weights(mt, "t", held)[:, :dim]
+      want = np.stack([exp_rows[int(i)] for i in held])
+      print("partial admission %s call %d: max |row - truth| = %.3e" %
+            (route, s, float(np.abs(got.astype(np.float64) - want).max())))
+      np.testing.assert_allclose(got, want, rtol=0, atol=1e-5, err_msg="%s call %d" % (route, s))
+    mt.close()
