@@ -427,6 +427,13 @@ struct DedupWs {
     return uint32_t(2 * n / item_target() + n / (kStepLightMax + 1) + 2);
   }
   static uint32_t item_target() { return kItemTarget; }
+  // Entries of the preallocated item list.  The item workgroups (rd_apply_role, rd_gather_role) fetch entry w
+  // — header and run descriptors — BEFORE they compare w with the item count, and w advances by the number of
+  // item workgroups, which is at most max_items(n): the last fetch of a workgroup lies below items + max_items.
+  // (A list of max_items entries was read up to 61 KB past its end by a batch of 300 lists of 33 in 9900
+  // positions — 300 items, 320 item workgroups, 379 entries: an illegal memory access,
+  // tests/test_run_dedup_forms_gpu.py "edge-300x33".)
+  static size_t item_list_entries(int64_t n) { return 2 * size_t(max_items(n)); }
 
   // Arguments of a run dedup of ids[0, n), n <= 65 536; the caller enqueues rd_dedup (on its own or
   // inside step_fwd).  A dedup that was never built leaves the scratch dirty: clear first (the
@@ -450,8 +457,8 @@ struct DedupWs {
     r_btab_key.reserve(size_t(nblk) * kRdStride);
     r_btab_val.reserve(size_t(nblk) * kRdStride);
     r_seg.reserve(size_t(nblk) * kRdBlock);
-    r_item_hdr.reserve(max_items(n));
-    r_item_runs.reserve(size_t(max_items(n)) * 64);
+    r_item_hdr.reserve(item_list_entries(n));
+    r_item_runs.reserve(item_list_entries(n) * 64);
     RunView d{};
     d.hs = r_hs.p; d.hlist = r_hlist.p; d.cap_mask = C - 1;
     d.uslot = r_uslot.p; d.ucnt = r_ucnt.p; d.upos = r_upos.p; d.btab_key = r_btab_key.p; d.btab_val = r_btab_val.p; d.seg = r_seg.p;

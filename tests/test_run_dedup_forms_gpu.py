@@ -1,0 +1,214 @@
+"""Both forms of the RUN dedup of the pipelined single-table step at every size edge (-m gpu):
+``rd_dedup_role`` (1024 threads: ``mhte_step_dedup`` and the forward launch) and ``rd_dedup4_role`` (256 threads,
+four positions each, in ``step_bwd_kernel`` when ``forward`` is given ``ahead_ids``), the three-workspace rotation
+of ``SparseStep`` and ``mhte_table_step_backward_ahead`` (csrc/mhte_step_kernels.h).
+
+The batches are those of tests/run_dedup_truth.py, which puts a case on each side of every constant of the two
+roles (the table at the top of that file; tests/test_run_dedup_truth_cpu.py asserts that they do).  Every case is
+a pipeline of 4 steps (6 batches of the same structure, consecutive seeds) run in three modes:
+  one    forward(b[s], next_ids=b[s+1])                       the 1024-thread role, in the forward launch
+  two    forward(b[s], next_ids=b[s+1], ahead_ids=b[s+2])     batches 2.. from the 256-thread role
+  mixed  ahead_ids on even steps only                          both roles and both forward forms alternate
+against the CPU oracle, step by step, and against each other bit for bit.
+
+Bars.  INTEGER gradients in [-8, 8] on an SGD table (zeros, lr 1, dim 4): every partial sum is an integer below
+2^24, so every association of a sum has the same bits and a dropped, doubled or misrouted occurrence cannot hide —
+everything exact.  Normal gradients on an Adagrad table (dim 16): bit for bit with ``exact_order=True`` (which is
+what sees a wrong order inside a run); otherwise RTOL_TREE / ATOL_SUM of tests/test_parity_gpu.py (measured and
+recorded there), the rows of ids that are light in every batch bit for bit."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import oracle as O  # noqa: E402
+import run_dedup_truth as R  # noqa: E402
+from monolith_amd import _lib, synthetic as S  # noqa: E402
+from monolith_amd.fused_step import SparseStep  # noqa: E402
+from test_parity_gpu import (ATOL_SUM, RTOL_TREE, _oracle_step, adagrad_cfg, ids_t, make, sgd_cfg,  # noqa: E402
+                             val_t)
+
+STEPS = 4
+MODES = ("one", "two", "mixed")
+INT_DIM, NORMAL_DIM = 4, 16
+NORMAL_LR, NORMAL_ACC = 0.05, 0.1
+
+
+def _np(t):
+  return t.cpu().numpy()
+
+
+def _bits(a):
+  return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _hands_over_two(mode, s):
+  return mode == "two" or (mode == "mixed" and s % 2 == 0)
+
+
+# ---------------------------------------------------------------------------------------------- a pipeline
+class Pipeline:
+  """The batches of a case, its gradients, and what the oracle makes of them: the rows ``forward`` must return
+  at every step, the distinct ids of every batch (sorted), the final rows of every id seen."""
+
+  def __init__(self, batches, kind):
+    assert len(batches) == STEPS + 2 and len({b.size for b in batches}) == 1
+    self.batches, self.kind, self.n = batches, kind, batches[0].size
+    n = self.n
+    if kind == "int":
+      self.dim, self.lr = INT_DIM, 1.0
+      self.grads = [np.random.default_rng(900 + s).integers(-8, 9, size=(n, INT_DIM)).astype(np.float32)
+                    for s in range(STEPS)]
+      ot = O.Table(O.segment(INT_DIM, O.OPT_SGD), 1)
+    else:
+      self.dim, self.lr = NORMAL_DIM, NORMAL_LR
+      self.grads = [(S.grad_batch(s, n, NORMAL_DIM) * 10).astype(np.float32) for s in range(STEPS)]
+      ot = O.Table(O.segment(NORMAL_DIM, O.OPT_ADAGRAD, p=(NORMAL_ACC, 0.0)), 1)
+    self.emb, self.uniq = [], []
+    for s in range(STEPS):
+      self.emb.append(ot.lookup(batches[s])[0].copy())
+      self.uniq.append(np.unique(batches[s]))
+      _oracle_step(ot, batches[s], self.grads[s], self.dim, self.lr, S.update_time(s))
+    self.probe = np.unique(np.concatenate(batches[:STEPS]))
+    self.rows = ot.lookup(self.probe)[0].copy()
+    self.size = ot.size()
+    assert self.size == self.probe.size
+    if kind == "int":   # the premise of the exact bar
+      assert np.abs(self.rows).max() < 2 ** 24 and (self.rows == np.round(self.rows)).all()
+    # ids with at most 32 occurrences in every batch: summed sequentially in either order
+    cnt_max = {}
+    for b in batches[:STEPS]:
+      for k, c in zip(*[a.tolist() for a in np.unique(b, return_counts=True)]):
+        cnt_max[k] = max(cnt_max.get(k, 0), c)
+    self.light = np.array([cnt_max[k] <= R.LIGHT_MAX for k in self.probe.tolist()])
+    self.dev = [ids_t(b) for b in batches]
+    self.grads_dev = [val_t(g) for g in self.grads]
+
+  def table(self):
+    return make({"emb": sgd_cfg(self.dim) if self.kind == "int" else adagrad_cfg(self.dim, NORMAL_LR, NORMAL_ACC)})
+
+  def check_rows(self, got, exp, exact, what):
+    if self.kind == "int" or exact:
+      np.testing.assert_array_equal(got, exp, err_msg=what)
+    else:
+      np.testing.assert_allclose(got, exp, rtol=RTOL_TREE, atol=ATOL_SUM, err_msg=what)
+
+  def check_step(self, step, s, emb, exact, what):
+    """forward's rows, the distinct-id count and the unique-id buffer of the current slot."""
+    self.check_rows(_np(emb), self.emb[s], exact, "%s: rows of forward, step %d" % (what, s))
+    nu = step.n_unique()
+    assert nu == self.uniq[s].size, "%s: n_unique, step %d" % (what, s)
+    uids = _np(step._uids[step._cur][:nu])  # pylint: disable=protected-access
+    np.testing.assert_array_equal(np.sort(uids), self.uniq[s], err_msg="%s: unique ids, step %d" % (what, s))
+
+  def check_end(self, mt, exact, what):
+    got = _np(mt.lookup({"emb": ids_t(self.probe)})["emb"])
+    self.check_rows(got, self.rows, exact, "%s: final rows" % what)
+    if self.kind != "int" and not exact:
+      np.testing.assert_array_equal(got[self.light], self.rows[self.light], err_msg="%s: light ids" % what)
+    assert mt.size("emb") == self.size, what
+    return got
+
+  def run(self, mode, exact=False):
+    """The pipeline in one mode, checked against the oracle step by step; the final rows."""
+    mt = self.table()
+    step = SparseStep(mt, "emb", self.n, exact_order=exact)
+    what = "mode %s%s" % (mode, ", exact order" if exact else "")
+    for s in range(STEPS):
+      ahead = self.dev[s + 2] if _hands_over_two(mode, s) else None
+      emb = step.forward(self.dev[s], next_ids=self.dev[s + 1], ahead_ids=ahead)
+      self.check_step(step, s, emb, exact, what)
+      step.backward(self.grads_dev[s], S.update_time(s))
+    return self.check_end(mt, exact, what)
+
+
+def _pipeline(name, kind):
+  batches = [R.build(name, seed) for seed in R.pipeline_seeds(name)]
+  return Pipeline(batches, kind)
+
+
+def _all_modes_agree(p, modes, exact):
+  rows = {mode: p.run(mode, exact) for mode in modes}
+  for mode in modes[1:]:   # the two roles leave the same format, so the summation trees are the same
+    np.testing.assert_array_equal(_bits(rows[mode]), _bits(rows[modes[0]]),
+                                  err_msg="final rows of mode %s | %s" % (mode, modes[0]))
+
+
+# ================================================================== a. integer gradients: everything exact
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_integer_gradients_every_mode_equals_oracle(name):
+  _all_modes_agree(_pipeline(name, "int"), MODES, exact=False)
+
+
+# ====================================================== b. normal gradients: the order inside runs and lists
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("name", R.names("run", "long", "reserved", "edge"))
+def test_normal_gradients_both_roles_equal_oracle(name, exact):
+  _all_modes_agree(_pipeline(name, "normal"), ("one", "two"), exact)
+
+
+# ================================================= c. a batch refilled in place after it was handed over
+def test_batch_refilled_in_place_after_it_was_deduplicated_two_ahead():
+  """The buffer of batch 2 is handed over as ``ahead_ids`` at step 0, whose backward launch deduplicates it,
+  and is then refilled in place (``copy_`` on the same stream).  The version check of ``_batch_key`` no longer
+  matches, so step 1 must deduplicate the new contents (in its forward launch) and the workspace that holds
+  the stale, never-built dedup must be cleared before it is used again (by step 1's backward launch)."""
+  name, other = "edge-40=20+20", "edge-32=31+1"
+  batches = [R.build(name, seed) for seed in R.pipeline_seeds(name)]
+  stale = batches[2]
+  batches[2] = R.build(other, R.pipeline_seeds(other)[2])
+  assert stale.size == batches[2].size and np.unique(stale).size != np.unique(batches[2]).size
+  assert not np.isin(stale, np.concatenate(batches)).any()
+  p = Pipeline(batches, "int")
+  buf = ids_t(stale)
+  dev = list(p.dev)
+  dev[2] = buf
+  mt = p.table()
+  step = SparseStep(mt, "emb", p.n)
+  for s in range(STEPS):
+    emb = step.forward(dev[s], next_ids=dev[s + 1], ahead_ids=dev[s + 2])
+    p.check_step(step, s, emb, False, "refilled")
+    step.backward(p.grads_dev[s], S.update_time(s))
+    if s == 0:
+      assert step._slot_of(step._batch_key(buf)) is not None   # pylint: disable=protected-access
+      buf.copy_(p.dev[2])
+      assert step._slot_of(step._batch_key(buf)) is None       # pylint: disable=protected-access
+  p.check_end(mt, False, "refilled")     # (no id of the stale contents: the sizes are equal)
+
+
+# ========================================================= d. refusals of mhte_table_step_backward_ahead
+def test_refused_backward_ahead_changes_nothing():
+  """``ws_ahead`` equal to ``ws`` or to ``ws_next``, and ``ws_ahead`` without ``ahead_ids``: refused with
+  MHTE_INVALID_ARGUMENT before anything changes — no update time noted, no dedup begun, nothing applied.  Every
+  step of a pipeline of two batches of look-ahead is first issued wrongly in the three ways (with another
+  gradient and another update time), then correctly; it ends on the oracle's rows exactly."""
+  p = _pipeline("edge-33=17+16", "int")
+  mt = p.table()
+  step = SparseStep(mt, "emb", p.n)
+  wrong_grads = val_t(np.full((p.n, p.dim), 3.0, np.float32))
+  for s in range(STEPS):
+    emb = step.forward(p.dev[s], next_ids=p.dev[s + 1], ahead_ids=p.dev[s + 2])
+    p.check_step(step, s, emb, False, "refusals")
+    cur, nxt = step._cur, step._nxt                      # pylint: disable=protected-access
+    ah = step._free_slot(cur, nxt)                        # pylint: disable=protected-access
+    ws, uids, nu = step._ws, step._uids, step._nu         # pylint: disable=protected-access
+
+    def backward_ahead(ws_ahead, ahead_ids):
+      mt.table_step_backward(step.idx, ws[cur], ws[nxt], uids[cur], nu[cur], wrong_grads, step.grad_u, step.lrs,
+                             S.update_time(s) + 10**6, ws_ahead=ws_ahead, ahead_ids=ahead_ids,
+                             uids_ahead=uids[ah], n_unique_ahead=nu[ah])
+
+    for ws_ahead, ahead_ids, message in ((ws[cur], p.dev[s + 2], "third one"),
+                                         (ws[nxt], p.dev[s + 2], "third one"),
+                                         (ws[ah], None, "null argument for the batch two ahead")):
+      with pytest.raises(_lib.InvalidArgumentError, match=message) as e:
+        backward_ahead(ws_ahead, ahead_ids)
+      assert e.value.code == _lib.MHTE_INVALID_ARGUMENT
+    step.backward(p.grads_dev[s], S.update_time(s))
+  p.check_end(mt, False, "refusals")
