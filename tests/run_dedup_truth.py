@@ -14,7 +14,11 @@ The constants mirrored here, and the cases that put a batch on each side of them
   kLongRun       32    bitmap rank | counting rank of a run         runs of 31, 32, 33, 34
    = kLightMax = kStepLightMax   list in ``hlist`` | work items     totals 32 | 33 | 40 over several workgroups
   kMaxLongRuns   16    bitmaps per workgroup                        16, 17 and 31 runs of 33 in one workgroup
-  kItemTarget    256   entries per heavy work item                  lists of 255, 256, 257; 256 | 257 over 8 workgroups
+  kItemTarget    256   EXPECTED entries per heavy work item: no     lists of 255, 256, 257 in one workgroup and over 8
+                       edge at 256.  ``rd_item_blocks`` keeps a     are all ONE item of up to 64 workgroups; the edges
+                       list of <= 512 whole and cuts a longer one   512 | 513 and 1024 | 1025 (and 2048 | 2049, 4096 |
+                       into power-of-two ranges of workgroups       4097 of the multi-table step's target of 1024) are
+                       (513: 16 per item, 1025: 8)                  the ``cut`` family of tests/multi_step_truth.py
   kRdMaxBlocks   64    workgroups per batch                         n = 64 513, 65 535, 65 536
   (count field)  11 bits of the packed LDS word of the 256 form     a run of exactly 1024
   kEmptyKey      INT64_MIN, kept in the side entry / side slot      ``reserved_batch``
@@ -275,6 +279,24 @@ def edge_key(ids, kind):
   hit = [k for k, c in totals(ids).items() if c == want]
   assert len(hit) == 1, (kind, hit)
   return hit[0]
+
+
+# ------------------------------------------------------------------------------- rows that name their id
+NAME_LIMIT = 2 ** 22          # every element of a naming row is an integer below this
+NAME_TINY = 2.0 ** -40        # scale of the naming rows of a table with real-valued updates: exact in fp32, and
+                              # far below the rounding of an update of ~1e-2, which it therefore does not blunt
+
+
+def naming_rows(ids, dim, seed, scale=1.0):
+  """(the distinct ids, sorted; rows [k, dim]): row of an id = (a number unique to the id + the column index)
+  * scale — assigned to a table before a pipeline starts, every element of every forward output then says
+  whose row it is (a pipeline's ids are new in every batch: without it every forward returns the initializer's
+  zeros, and a row scattered to the wrong occurrence is not seen)."""
+  u = np.unique(np.asarray(ids, np.int64))
+  base = 1 + np.random.default_rng(seed).permutation(u.size)
+  rows = base[:, None] + np.arange(dim)[None, :]
+  assert rows.max() < NAME_LIMIT
+  return u, (rows.astype(np.float64) * scale).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ registry

@@ -11,7 +11,9 @@ a pipeline of 4 steps (6 batches of the same structure, consecutive seeds) run i
   mixed  ahead_ids on even steps only                          both roles and both forward forms alternate
 against the CPU oracle, step by step, and against each other bit for bit.
 
-Bars.  INTEGER gradients in [-8, 8] on an SGD table (zeros, lr 1, dim 4): every partial sum is an integer below
+Bars.  Every id of a pipeline is assigned a row that names it before the first step (``naming_rows``: the batches
+draw fresh ids, so ``forward`` would otherwise return zeros everywhere and see no misrouted row).  INTEGER gradients
+in [-8, 8] on an SGD table (lr 1, dim 4): every row and partial sum is an integer below
 2^24, so every association of a sum has the same bits and a dropped, doubled or misrouted occurrence cannot hide —
 everything exact.  Normal gradients on an Adagrad table (dim 16): bit for bit with ``exact_order=True`` (which is
 what sees a wrong order inside a run); otherwise RTOL_TREE / ATOL_SUM of tests/test_parity_gpu.py (measured and
@@ -70,6 +72,13 @@ class Pipeline:
       self.dim, self.lr = NORMAL_DIM, NORMAL_LR
       self.grads = [(S.grad_batch(s, n, NORMAL_DIM) * 10).astype(np.float32) for s in range(STEPS)]
       ot = O.Table(O.segment(NORMAL_DIM, O.OPT_ADAGRAD, p=(NORMAL_ACC, 0.0)), 1)
+    # rows that name their id, assigned before the pipeline starts (here and in ``table``): every batch draws
+    # fresh ids, so the rows ``forward`` returns would otherwise be the initializer's zeros everywhere and a row
+    # scattered to the wrong occurrence would pass.  Integers for the integer bar; for the normal gradients the
+    # same integers scaled far below the rounding of an update.
+    self.named_ids, self.named_rows = R.naming_rows(np.concatenate(batches[:STEPS]), self.dim, 4242,
+                                                    1.0 if kind == "int" else R.NAME_TINY)
+    ot.assign(self.named_ids, self.named_rows, S.update_time(0))
     self.emb, self.uniq = [], []
     for s in range(STEPS):
       self.emb.append(ot.lookup(batches[s])[0].copy())
@@ -91,7 +100,9 @@ class Pipeline:
     self.grads_dev = [val_t(g) for g in self.grads]
 
   def table(self):
-    return make({"emb": sgd_cfg(self.dim) if self.kind == "int" else adagrad_cfg(self.dim, NORMAL_LR, NORMAL_ACC)})
+    mt = make({"emb": sgd_cfg(self.dim) if self.kind == "int" else adagrad_cfg(self.dim, NORMAL_LR, NORMAL_ACC)})
+    mt.assign({"emb": (ids_t(self.named_ids), val_t(self.named_rows))}, req_time=S.update_time(0))
+    return mt
 
   def check_rows(self, got, exp, exact, what):
     if self.kind == "int" or exact:
