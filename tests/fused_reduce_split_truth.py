@@ -6,10 +6,13 @@ reference kernel (`sum = T(0); sum += ...`) and of the CPU op (accumulation into
 vectorised over the batch rows and looped over the position inside the row."""
 import json
 import os
+import re
 
 import numpy as np
 
-KAT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fused_reduce_split_kat.json")
+_HERE = os.path.dirname(os.path.abspath(__file__))
+KAT = os.path.join(_HERE, "golden", "fused_reduce_split_kat.json")
+KERNELS_H = os.path.join(_HERE, "..", "monolith_amd", "csrc", "mhte_pool_split_kernels.h")
 
 
 def load_kat():
@@ -23,21 +26,39 @@ def splits_of_sorted(id_indices, batch):
 
 
 def truth_forward(row_splits, emb, slice_dims):
-  """-> list of [bs, d] float32 arrays, one per slice of this feature."""
+  """-> list of [bs, d] float32 arrays, one per slice of this feature (monotone row_splits inside the matrix)."""
   rs = np.asarray(row_splits, np.int64)
+  return truth_forward_ranges(rs[:-1], rs[1:], emb, slice_dims)
+
+
+def truth_forward_ranges(s0, s1, emb, slice_dims):
+  """The same chain for explicit ranges: batch row b sums emb[s0[b]:s1[b]] (empty where s1[b] <= s0[b]; the ranges
+  may overlap or run backwards through the matrix from one batch row to the next)."""
+  s0, s1 = np.asarray(s0, np.int64), np.asarray(s1, np.int64)
   emb = np.asarray(emb, np.float32)
-  bs, dim = rs.size - 1, emb.shape[1]
-  assert sum(slice_dims) == dim
-  lens = rs[1:] - rs[:-1]
+  bs, dim = s0.size, emb.shape[1]
+  assert s1.size == bs and sum(slice_dims) == dim
+  lens = np.maximum(s1 - s0, 0)
+  assert bs == 0 or (s0[lens > 0].min(initial=0) >= 0 and s1[lens > 0].max(initial=0) <= emb.shape[0])
   acc = np.zeros((bs, dim), np.float32)   # +0
   order = np.argsort(-lens, kind="stable")   # batch rows, longest first: the rows with a p-th id are a prefix
   by_len = lens[order]
   for p in range(int(lens.max()) if bs else 0):
     k = int(np.searchsorted(-by_len, -p, side="left"))   # rows with lens > p
     rows = order[:k]
-    acc[rows] = acc[rows] + emb[rs[rows] + p]   # one fp32 add per element, in row order
+    acc[rows] = acc[rows] + emb[s0[rows] + p]   # one fp32 add per element, in row order
   cuts = np.cumsum(slice_dims)[:-1]
   return [np.ascontiguousarray(a) for a in np.split(acc, cuts, axis=1)]
+
+
+def clamped_splits(rs, n_rows):
+  """The ranges the kernels make of ANY row_splits (the header's contract, "Ranges are clamped to
+  [0, emb_rows[i]]"): s0[b] = clamp(rs[b], 0, n), s1[b] = clamp(rs[b + 1], s0[b], n).  -> (s0, s1), int64 [bs]."""
+  rs = np.asarray(rs, np.int64)
+  n = int(n_rows)
+  s0 = np.minimum(np.maximum(rs[:-1], 0), n)
+  s1 = np.minimum(np.maximum(rs[1:], s0), n)
+  return s0, s1
 
 
 def truth_gradient(row_splits, n_rows, slice_grads):
@@ -49,6 +70,20 @@ def truth_gradient(row_splits, n_rows, slice_grads):
   lens = rs[1:] - rs[:-1]
   rowids = np.repeat(np.arange(rs.size - 1), lens)
   out[rs[0]:rs[-1]] = g[rowids]
+  return out
+
+
+def truth_gradient_ranges(s0, s1, n_rows, slice_grads):
+  """The gradient for explicit DISJOINT ranges (`clamped_splits` of monotone row_splits): rows s0[b] .. s1[b] - 1
+  take batch row b's slice gradients, every other row is +0."""
+  s0, s1 = np.asarray(s0, np.int64), np.asarray(s1, np.int64)
+  g = np.concatenate([np.asarray(x, np.float32) for x in slice_grads], axis=1)
+  out = np.zeros((n_rows, g.shape[1]), np.float32)
+  seen = np.zeros(n_rows, bool)
+  for b in range(s0.size):
+    assert not seen[s0[b]:s1[b]].any(), "overlapping ranges: two batch rows would own row(s) of the gradient"
+    seen[s0[b]:s1[b]] = True
+    out[s0[b]:s1[b]] = g[b]
   return out
 
 
@@ -86,3 +121,122 @@ def order_sensitive_case(seed, bs, n_features=26, long_row=2048):
       emb[rs[7]:rs[8]] = -0.0
     feats.append({"row_splits": rs, "emb": emb, "slice_dims": SLICES[dim]})
   return feats
+
+
+# ---- the planner's documented rules, mirrored ------------------------------------------------------------
+# (reduce_split_launch in csrc/mhte.hip.  The mirror only guards the INTENT of the forms cases — a case asserts
+# through it that its shape still selects the form it is named for; it proves nothing about the kernel, the bit
+# comparison does that.)
+_CONSTANTS = ("kSplitInlineUnits", "kSplitInlineSlices", "kSplitUnitCols", "kSplitDeep")
+
+
+def kernel_constants():
+  """The planner's constants, read from csrc/mhte_pool_split_kernels.h."""
+  with open(KERNELS_H) as f:
+    text = f.read()
+  return {name: int(re.search(r"\b%s\s*=\s*(\d+)" % name, text).group(1)) for name in _CONSTANTS}
+
+
+def plan(dims, slice_dims, aligned, bs):
+  """dims[i], slice_dims[i] (a list) and aligned[i] (every pointer of feature i 16-byte aligned; one bool for all)
+  -> {"features": [{"vec": bool, "units": [(col0, width, log2g), ...]}], "n_units", "n_slices", "ext", "need",
+  "gx"}: float4 lane columns where the dim and every slice start and width are multiples of 4 and the pointers
+  aligned, else floats; units of kSplitUnitCols lane columns; lanes per batch row = the next power of two; tables
+  in device memory beyond kSplitInlineUnits units or kSplitInlineSlices slices; gx = min(row blocks the widest
+  unit needs, max(64, 32768 / units) capped at 4096)."""
+  k = kernel_constants()
+  aligned = [aligned] * len(dims) if isinstance(aligned, (bool, np.bool_)) else list(aligned)
+  assert len(dims) == len(slice_dims) == len(aligned)
+  feats, n_units, need = [], 0, 1
+  for dim, sl, al in zip(dims, slice_dims, aligned):
+    assert sum(sl) == dim and dim > 0
+    starts = np.concatenate([[0], np.cumsum(sl)[:-1]])
+    vec = bool(al) and dim % 4 == 0 and all((int(s) | int(d)) % 4 == 0 for s, d in zip(starts, sl))
+    per = 4 if vec else 1
+    cols, units = dim // per, []
+    for c0 in range(0, cols, k["kSplitUnitCols"]):
+      nc = min(k["kSplitUnitCols"], cols - c0)
+      log2g = 0
+      while (1 << log2g) < nc:
+        log2g += 1
+      groups = 256 >> log2g
+      need = max(need, (bs + groups - 1) // groups)
+      units.append((c0 * per, nc * per, log2g))
+    n_units += len(units)
+    feats.append({"vec": vec, "units": units})
+  n_slices = sum(len(s) for s in slice_dims)
+  cap = min(4096, max(64, 32768 // n_units))
+  return {"features": feats, "n_units": n_units, "n_slices": n_slices, "need": need, "gx": min(need, cap),
+          "ext": n_units > k["kSplitInlineUnits"] or n_slices > k["kSplitInlineSlices"]}
+
+
+def plan_of(feats, aligned=True):
+  bs = feats[0]["row_splits"].size - 1
+  return plan([f["emb"].shape[1] for f in feats], [f["slice_dims"] for f in feats], aligned, bs)
+
+
+def lane_kinds(p):
+  """-> {(vec, log2g)} over the units of a plan."""
+  return {(f["vec"], u[2]) for f in p["features"] for u in f["units"]}
+
+
+# ---- seeded inputs of the forms cases (tests/test_fused_reduce_split_forms_gpu.py) --------------------------
+# row lengths on both sides of the 16-deep loop and of its 4-wide tail
+LENGTH_CYCLE = (0, 1, 3, 4, 5, 15, 16, 17, 19, 20, 31, 32, 33, 36, 48)
+LANE_VEC_DIMS = (4, 8, 12, 16, 20, 32, 36, 64, 68, 128, 132, 256)   # one slice each: 1 .. 64 float4 lanes
+LANE_SCALAR = ((1, [1]), (2, [2]), (3, [3]), (5, [5]), (8, [3, 5]), (9, [9]), (17, [17]), (33, [33]), (64, [1, 63]))
+WIDE = ((260, [8, 252]), (516, [256, 4, 256]), (65, [65]), (129, [64, 1, 64]), (200, [7, 193]))
+
+
+def scaled_normal(rng, shape):
+  """normal * 2**randint(-20, 20): any re-association of a sum changes bits."""
+  return (rng.standard_normal(shape) * np.exp2(rng.integers(-20, 21, size=shape))).astype(np.float32)
+
+
+def cycle_lengths(bs, shift=0):
+  return np.array([LENGTH_CYCLE[(b + shift) % len(LENGTH_CYCLE)] for b in range(bs)], np.int64)
+
+
+def feature(rng, lens, dim, slice_dims, head=0, tail=0):
+  """One feature whose batch row b has lens[b] rows, `head` rows before the first range and `tail` after the
+  last.  -> the dict of `order_sensitive_case`."""
+  rs = (head + np.concatenate([[0], np.cumsum(lens)])).astype(np.int32)
+  n = int(rs[-1]) + tail
+  return {"row_splits": rs, "emb": scaled_normal(rng, (n, dim)), "slice_dims": list(slice_dims)}
+
+
+def cycle_case(rng, shapes, bs, head_tail=None):
+  """A feature per (dim, slice_dims) of `shapes`, the length cycle shifted by one from feature to feature."""
+  head_tail = head_tail or {}
+  return [feature(rng, cycle_lengths(bs, i), dim, sl, *head_tail.get(dim, (0, 0)))
+          for i, (dim, sl) in enumerate(shapes)]
+
+
+def lane_group_case(tables="inline", seed=121, bs=37):
+  """Case 1: both lane kinds at every log2g from 0 to 6 in 21 units and 23 slices; the float4 dim-36 and the
+  scalar dim-17 feature leave a head of 3 and a tail of 5 rows uncovered; the scalar dim-9 feature has a row of
+  16 and a row of 17 addends that are all -0.0.  tables: "inline"; "ext_units" appends 12 float4 features of
+  dim 16 (33 units); "ext_slices" one float4 feature of dim 400 in 100 slices of 4 (123 slices, 23 units).  The
+  first 21 features are the same data whatever `tables` is.  (The seed is one for which every range of 3 or more
+  addends of every feature at least 8 columns wide changes bits when its rows are reversed: tests/
+  test_fused_reduce_split_cpu.py.)"""
+  shapes = [(d, [d]) for d in LANE_VEC_DIMS] + [(d, list(s)) for d, s in LANE_SCALAR]
+  shapes += {"inline": [], "ext_units": [(16, [16])] * 12, "ext_slices": [(400, [4] * 100)]}[tables]
+  feats = cycle_case(np.random.default_rng(seed), shapes, bs, {36: (3, 5), 17: (3, 5)})
+  f = feats[[d for d, _ in shapes].index(9)]
+  lens = np.diff(f["row_splits"])
+  for want in (16, 17):
+    b = int(np.flatnonzero(lens == want)[0])
+    f["emb"][f["row_splits"][b]:f["row_splits"][b + 1]] = -0.0
+  return feats
+
+
+def wide_case(seed=102, bs=37):
+  """Case 2: features wider than one unit (col0 > 0, a narrower last unit, slices across and at unit edges)."""
+  return cycle_case(np.random.default_rng(seed), [(d, list(s)) for d, s in WIDE], bs)
+
+
+def slice_grads_of(rng, feats):
+  """Standard-normal [bs, d] per slice -> a list per feature."""
+  bs = feats[0]["row_splits"].size - 1
+  return [[rng.standard_normal((bs, d)).astype(np.float32) for d in f["slice_dims"]] for f in feats]
