@@ -89,6 +89,31 @@ struct DevBuf {
   }
 };
 
+// device memory of one call on one stream: from the stream's pool (hipMalloc where the pool refuses), freed in
+// stream order behind the kernels that read it (where that fails: synchronise, hipFree)
+struct StreamTmp {
+  char* d = nullptr;
+  hipStream_t st;
+  explicit StreamTmp(hipStream_t s) : st(s) {}
+  StreamTmp(const StreamTmp&) = delete;
+  StreamTmp& operator=(const StreamTmp&) = delete;
+  ~StreamTmp() {
+    if (d && hipFreeAsync(d, st) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(st);
+      (void)hipFree(d);
+    }
+  }
+  char* alloc(size_t bytes) {   // (once per object)
+    void* p = nullptr;
+    if (hipMallocAsync(&p, bytes, st) != hipSuccess) {
+      (void)hipGetLastError();
+      HIP_OK(hipMalloc(&p, bytes));
+    }
+    return d = static_cast<char*>(p);
+  }
+};
+
 // pinned host staging (device <-> host copies at link speed, not through a pageable bounce buffer)
 template <class T>
 struct HostBuf {
@@ -1949,6 +1974,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_fi_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
+#include "mhte_layout_host.h"
 #include "mhte_ckpt_host.h"
 
 struct mhte_multi_step {
@@ -2879,9 +2905,10 @@ mhte_status mhte_reduce_rows(const int64_t* indices, const float* values, int64_
       }
     } else {
       HIP_OK(hipMemsetAsync(out, 0, size_t(batch) * dim * sizeof(float), st));
+      StreamTmp tmp(st);
       uint32_t* cnt = nullptr;
       if (mode == 1) {
-        HIP_OK(hipMallocAsync(reinterpret_cast<void**>(&cnt), size_t(batch) * 4, st));
+        cnt = reinterpret_cast<uint32_t*>(tmp.alloc(size_t(batch) * 4));
         HIP_OK(hipMemsetAsync(cnt, 0, size_t(batch) * 4, st));
       }
       if (n)
@@ -2890,7 +2917,6 @@ mhte_status mhte_reduce_rows(const int64_t* indices, const float* values, int64_
       if (mode != 0)
         reduce_rows_finish_kernel<<<dim3(uint32_t((batch * dim + 255) / 256)), 256, 0, st>>>(
             out, cnt, batch, dim, mode);
-      if (cnt) HIP_OK(hipFreeAsync(cnt, st));
     }
     HIP_OK(hipGetLastError());
   });
@@ -3010,29 +3036,13 @@ static void reduce_split_launch(bool forward, const int32_t* row_splits, const i
   A.row_splits = row_splits;
   A.bs = bs;
   const bool ext = units.size() > size_t(kSplitInlineUnits) || slices.size() > size_t(kSplitInlineSlices);
-  struct Tmp {   // (freed in stream order behind the kernels that read it)
-    char* d = nullptr;
-    hipStream_t st;
-    ~Tmp() {
-      if (d && hipFreeAsync(d, st) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(d);
-      }
-    }
-  } tmp;
-  tmp.st = st;
+  StreamTmp tmp(st);   // (freed in stream order behind the kernels that read it)
   if (ext) {
     const size_t o_slice = units.size() * sizeof(SplitUnit), total = o_slice + slices.size() * sizeof(SplitSlice);
     std::vector<char> h(total);
     memcpy(h.data(), units.data(), o_slice);
     memcpy(h.data() + o_slice, slices.data(), total - o_slice);
-    void* d = nullptr;
-    if (hipMallocAsync(&d, total, st) != hipSuccess) {
-      (void)hipGetLastError();
-      HIP_OK(hipMalloc(&d, total));
-    }
-    tmp.d = static_cast<char*>(d);
+    tmp.alloc(total);
     PinnedStage::of(current_device()).upload(tmp.d, h.data(), total, st);   // (no wait for the stream)
     A.x_units = reinterpret_cast<const SplitUnit*>(tmp.d);
     A.x_slices = reinterpret_cast<const SplitSlice*>(tmp.d + o_slice);
@@ -4026,413 +4036,7 @@ mhte_status mhte_table_set_count_hits(mhte_multi_table* t, int32_t table, int32_
   });
 }
 
-// ---- fused_embedding_to_layout ------------------------------------------------------------------
-extern "C++" {
-namespace mhte {
-static void layout_launch(bool forward, const float* const* embeddings, const int32_t* emb_stride,
-                          const int64_t* emb_count, int32_t n_emb, const unsigned long long* fid_offset,
-                          int64_t n_fid, const int32_t* feature_offset, int64_t n_feature,
-                          const uint32_t* nfl_offset, int32_t n_nfl, int32_t batch,
-                          const mhte_layout_slice* slices, int32_t n_slices, float* const* outputs,
-                          const int64_t* output_len, int32_t n_outputs, int32_t flags, hipStream_t st) {
-  if (n_emb < 0 || n_outputs < 0 || n_emb > (1 << 20) || n_outputs > (1 << 20))
-    throw Error(MHTE_INVALID_ARGUMENT, "layout: bad matrix / output count");
-  if (batch < 0 || n_slices < 0 || n_fid > INT32_MAX || n_feature > INT32_MAX)
-    throw Error(MHTE_INVALID_ARGUMENT, "layout: bad sizes");
-  // Few matrices and outputs (a model's tables: the training path) travel in the kernel arguments.
-  // More of them (one matrix per (table, shard, feature) as the reference's parameter-server path
-  // hands them over: ~1000 in its own test) go through pointer tables uploaded for the call.
-  const bool ext = n_emb > kMaxLayoutEmb || n_outputs > kMaxLayoutOut;
-  struct Blob {
-    char* d = nullptr;
-    hipStream_t st;
-    ~Blob() {
-      if (d && hipFreeAsync(d, st) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(d);
-      }
-    }
-  } blob;
-  blob.st = st;
-  // ---- forward, copy form, one launch: do the slices (plus zero runs for the columns between them) write
-  // every float of their outputs?  Then layout_rows_kernel writes the zeros too and the fill in front
-  // of it — a pass over the whole output: 268 MB at configs[4]'s shape — is left out for those outputs.
-  static const bool rows_form = !(getenv("MHTE_LAYOUT_ROWS") && atoi(getenv("MHTE_LAYOUT_ROWS")) == 0);
-  std::vector<char> out_written(size_t(std::max(n_outputs, 0)), 0);
-  std::vector<LayoutTask> zero_runs;
-  if (forward && !ext && rows_form && (flags & MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS) != 0 && n_fid == n_feature &&
-      n_slices > 0 && n_slices <= kMaxLayoutTasks && batch > 0) {
-    bool ok = true;
-    int64_t cols = 0;
-    for (int32_t i = 0; ok && i < n_slices; ++i) {
-      const mhte_layout_slice& sc = slices[i];
-      ok = sc.out_type != 2 && sc.pooling != kPoolFirstN && sc.out_index >= 0 && sc.out_index < n_outputs &&
-           sc.dim > 0 && sc.start >= 0 && sc.out_offset >= 0 && sc.out_row_floats > 0 &&
-           ((sc.start | sc.dim | sc.out_offset | sc.out_row_floats) & 3) == 0 && aligned16(outputs[sc.out_index]);
-      cols += sc.dim / 4;
-    }
-    for (int32_t i = 0; ok && i < n_emb; ++i) ok = (emb_stride[i] & 3) == 0 && aligned16(embeddings[i]);
-    std::vector<char> covered(size_t(n_outputs), 0);
-    for (int32_t o = 0; ok && o < n_outputs; ++o) {
-      std::vector<std::pair<int32_t, int32_t>> runs;   // (offset, width) of the slices of output o
-      int32_t stride = 0;
-      for (int32_t i = 0; ok && i < n_slices; ++i)
-        if (slices[i].out_index == o) {
-          if (stride && stride != slices[i].out_row_floats) ok = false;
-          stride = slices[i].out_row_floats;
-          runs.emplace_back(slices[i].out_offset, slices[i].dim);
-        }
-      if (!ok || runs.empty()) continue;
-      if (output_len[o] != int64_t(batch) * stride) continue;   // (rows beyond the batch: the fill stays)
-      std::sort(runs.begin(), runs.end());
-      int32_t pos = 0;
-      std::vector<LayoutTask> gaps;
-      bool tiles = true;
-      for (auto& r : runs) {
-        if (r.first < pos) { tiles = false; break; }            // overlapping slices: the fill stays
-        if (r.first > pos) {
-          LayoutTask z{};
-          z.nfl_idx = -2;
-          z.dim = r.first - pos;
-          z.pooling = kPoolZeroFill;
-          z.out_index = o;
-          z.out_offset = pos;
-          z.out_stride = stride;
-          gaps.push_back(z);
-        }
-        pos = r.first + r.second;
-      }
-      if (!tiles || pos > stride) continue;
-      if (pos < stride) {
-        LayoutTask z{};
-        z.nfl_idx = -2;
-        z.dim = stride - pos;
-        z.pooling = kPoolZeroFill;
-        z.out_index = o;
-        z.out_offset = pos;
-        z.out_stride = stride;
-        gaps.push_back(z);
-      }
-      int64_t gcols = 0;
-      for (auto& z : gaps) gcols += z.dim / 4;
-      if (size_t(n_slices) + zero_runs.size() + gaps.size() > size_t(kMaxLayoutTasks) ||
-          cols + gcols > kLayoutRowsMaxF)
-        continue;
-      cols += gcols;
-      zero_runs.insert(zero_runs.end(), gaps.begin(), gaps.end());
-      covered[size_t(o)] = 1;
-    }
-    if (ok && cols <= kLayoutRowsMaxF) out_written = covered;
-    else zero_runs.clear();
-  }
-  auto zero_buffers = [&](float* const* bufs, const int64_t* lens, int32_t n, const std::vector<char>* skip) {
-    LayoutZeroArgs Z{};
-    int32_t m = 0;
-    uint64_t longest = 0;
-    auto flush = [&] {
-      if (m == 0 || longest == 0) { m = 0; longest = 0; return; }
-      const uint32_t gx = uint32_t(std::min<uint64_t>(512, (longest + 4095) / 4096));
-      layout_zero_args_kernel<<<dim3(gx, uint32_t(m)), 256, 0, st>>>(Z);
-      HIP_OK(hipGetLastError());
-      m = 0;
-      longest = 0;
-    };
-    for (int32_t i = 0; i < n; ++i) {
-      if (lens[i] <= 0 || (skip && (*skip)[size_t(i)])) continue;
-      Z.p[m] = bufs[i];
-      Z.len[m] = uint64_t(lens[i]);
-      longest = std::max(longest, Z.len[m]);
-      if (++m == kLayoutZeroBufs) flush();
-    }
-    flush();
-  };
-  LayoutArgs A{};
-  if (ext) {
-    const size_t o_emb = 0, o_out = o_emb + size_t(n_emb) * 8, o_len = o_out + size_t(n_outputs) * 8,
-                 o_str = o_len + size_t(std::max(n_emb, n_outputs)) * 8, o_cnt = o_str + size_t(n_emb) * 4,
-                 total = o_cnt + size_t(n_emb) * 4;
-    std::vector<char> h(total, 0);
-    memcpy(h.data() + o_emb, embeddings, size_t(n_emb) * 8);
-    memcpy(h.data() + o_out, outputs, size_t(n_outputs) * 8);
-    uint64_t* len = reinterpret_cast<uint64_t*>(h.data() + o_len);
-    uint32_t* str = reinterpret_cast<uint32_t*>(h.data() + o_str);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(h.data() + o_cnt);
-    uint64_t longest = 0;
-    if (forward) for (int32_t i = 0; i < n_outputs; ++i) longest = std::max(longest, len[i] = uint64_t(std::max<int64_t>(0, output_len[i])));
-    else for (int32_t i = 0; i < n_emb; ++i) longest = std::max(longest, len[i] = uint64_t(std::max<int64_t>(0, emb_count[i])));
-    for (int32_t i = 0; i < n_emb; ++i) {
-      str[i] = uint32_t(emb_stride[i]);
-      cnt[i] = uint32_t(emb_count[i]);
-    }
-    void* d = nullptr;
-    if (hipMallocAsync(&d, total, st) != hipSuccess) {
-      (void)hipGetLastError();
-      HIP_OK(hipMalloc(&d, total));
-    }
-    blob.d = static_cast<char*>(d);
-    PinnedStage::of(current_device()).upload(blob.d, h.data(), total, st);   // (no wait for the stream)
-    A.x_emb = reinterpret_cast<const float* const*>(blob.d + o_emb);
-    A.x_out = reinterpret_cast<float* const*>(blob.d + o_out);
-    A.x_stride = reinterpret_cast<const uint32_t*>(blob.d + o_str);
-    A.x_count = reinterpret_cast<const uint32_t*>(blob.d + o_cnt);
-    const int32_t nz = forward ? n_outputs : n_emb;   // SetZeroFunctor: rows without fids stay zero
-    if (nz > 0 && longest > 0) {
-      const uint32_t gx = uint32_t(std::min<uint64_t>(64, (longest + 1023) / 1024));
-      layout_zero_kernel<<<dim3(gx, uint32_t(nz)), 256, 0, st>>>(
-          reinterpret_cast<float* const*>(blob.d + (forward ? o_out : o_emb)),
-          reinterpret_cast<const uint64_t*>(blob.d + o_len));
-      HIP_OK(hipGetLastError());
-    }
-  } else {
-    // SetZeroFunctor: rows without fids stay zero (one launch over all buffers; outputs the copy launch
-    // below writes in full are left to it)
-    if (forward) zero_buffers(outputs, output_len, n_outputs, &out_written);
-    else zero_buffers(const_cast<float* const*>(embeddings), emb_count, n_emb, nullptr);
-  }
-  if (batch == 0 || n_slices == 0) return;
-  if (!ext) {
-    for (int32_t i = 0; i < n_emb; ++i) {
-      A.emb[i] = embeddings[i];
-      A.emb_stride[i] = uint32_t(emb_stride[i]);
-      A.emb_count[i] = uint32_t(emb_count[i]);
-    }
-    for (int32_t i = 0; i < n_outputs; ++i) A.out[i] = outputs[i];
-  }
-  A.fid_offset = fid_offset;
-  A.feature_offset = feature_offset;
-  A.nfl_offset = nfl_offset;
-  A.n_fid = int32_t(n_fid);
-  A.n_feature = int32_t(n_feature);
-  A.n_nfl = n_nfl;
-  A.batch = batch;
-  A.n_emb = n_emb;
-  auto check_slice = [&](int32_t i, int32_t first_of_addn) {
-    const mhte_layout_slice& sc = slices[i];
-    if (sc.out_index < 0 || sc.out_index >= n_outputs || sc.dim <= 0 || sc.out_row_floats <= 0 ||
-        int64_t(sc.out_offset) + int64_t(sc.dim) * (sc.pooling == 3 ? std::max(1, sc.max_sequence_length) : 1) >
-            sc.out_row_floats ||
-        int64_t(batch) * sc.out_row_floats > output_len[sc.out_index])
-      throw Error(MHTE_INVALID_ARGUMENT, "layout: slice " + std::to_string(i) + " does not fit its output");
-    if (sc.out_type == 2 && sc.pooling == 3)   // CHECK in the op's constructor
-      throw Error(MHTE_INVALID_ARGUMENT, "layout: FIRSTN pooling cannot be added (ADDN)");
-    if (sc.out_type == 2 && sc.dim != slices[first_of_addn].dim)
-      throw Error(MHTE_INVALID_ARGUMENT, "layout: slices of an ADDN layout differ in width");
-  };
-  auto task_of = [&](const mhte_layout_slice& sc) {
-    LayoutTask t{};
-    t.nfl_idx = sc.feature_idx;
-    t.start = sc.start;
-    t.dim = sc.dim;
-    t.pooling = sc.pooling;
-    t.max_seq = sc.max_sequence_length;
-    t.out_index = sc.out_index;
-    t.out_offset = sc.out_offset;
-    t.out_stride = sc.out_row_floats;
-    return t;
-  };
-  // ---- the gradient without float atomics (general form; MHTE_POOL_ATOMICS=1 keeps the atomic one)
-  // The flag's plain stores hold only while no element of a feature's row is named by two slices (the
-  // same columns of one feature in a CONCAT and in a STACK layout, say): there the gradient is a sum of
-  // two addends, and the call takes the form it would take without the flag.  The forward only reads.
-  bool copy_form = (flags & MHTE_LAYOUT_ONE_FID_UNIQUE_ROWS) != 0 && n_fid == n_feature;
-  if (!forward && copy_form) {
-    std::vector<std::pair<int32_t, int32_t>> order;   // (feature, slice) by feature, then start
-    order.reserve(size_t(n_slices));
-    for (int32_t i = 0; i < n_slices; ++i) order.emplace_back(slices[i].feature_idx, i);
-    std::sort(order.begin(), order.end(), [&](const std::pair<int32_t, int32_t>& a, const std::pair<int32_t, int32_t>& b) {
-      return a.first != b.first ? a.first < b.first : slices[a.second].start < slices[b.second].start;
-    });
-    int64_t end = 0;   // one past the last column a slice of the current feature has named so far
-    for (size_t i = 0; copy_form && i < order.size(); ++i) {
-      const mhte_layout_slice& sc = slices[order[i].second];
-      if (i == 0 || order[i].first != order[i - 1].first) end = INT64_MIN;
-      if (int64_t(sc.start) < end) copy_form = false;
-      end = std::max(end, int64_t(sc.start) + std::max(sc.dim, 0));
-    }
-  }
-  if (!forward && !copy_form && !pool_atomics() && n_fid > 0) {
-    std::vector<LayoutTask> tasks(static_cast<size_t>(n_slices));
-    std::vector<uint32_t> t_off(size_t(n_nfl) + 1, 0), t_idx;
-    for (int32_t i = 0, first = 0; i < n_slices; ++i) {
-      if (i == 0 || slices[i].out_type != 2 || slices[i - 1].out_type != 2 ||
-          slices[i].out_index != slices[i - 1].out_index)
-        first = i;
-      check_slice(i, first);
-      tasks[size_t(i)] = task_of(slices[i]);
-      if (slices[i].feature_idx >= 0 && slices[i].feature_idx < n_nfl) ++t_off[size_t(slices[i].feature_idx) + 1];
-    }
-    for (int32_t i = 0; i < n_nfl; ++i) t_off[size_t(i) + 1] += t_off[size_t(i)];
-    t_idx.resize(t_off[size_t(n_nfl)]);
-    {
-      std::vector<uint32_t> cur(t_off.begin(), t_off.end() - 1);
-      for (int32_t i = 0; i < n_slices; ++i)
-        if (slices[i].feature_idx >= 0 && slices[i].feature_idx < n_nfl)
-          t_idx[cur[size_t(slices[i].feature_idx)]++] = uint32_t(i);
-    }
-    const size_t o_task = 0, o_off = o_task + tasks.size() * sizeof(LayoutTask),
-                 o_idx = o_off + t_off.size() * 4, o_qf = (o_idx + t_idx.size() * 4 + 15) & ~size_t(15),
-                 o_qseq = o_qf + size_t(n_fid) * 4, o_fnfl = o_qseq + size_t(n_fid) * 4,
-                 o_kflag = o_fnfl + size_t(std::max<int64_t>(1, n_feature)) * 4,   // (zeroed from here)
-                 o_nheavy = o_kflag + size_t(n_fid) * 4, o_heavy = o_nheavy + 16,
-                 o_cpos = o_heavy + size_t(n_fid) * 4, total = o_cpos + size_t(n_fid) * 4;
-    struct Tmp {   // (freed in stream order behind the kernels that read it)
-      char* d = nullptr;
-      hipStream_t st;
-      ~Tmp() {
-        if (d && hipFreeAsync(d, st) != hipSuccess) {
-          (void)hipGetLastError();
-          (void)hipStreamSynchronize(st);
-          (void)hipFree(d);
-        }
-      }
-    } tmp;
-    tmp.st = st;
-    void* d = nullptr;
-    if (hipMallocAsync(&d, total, st) != hipSuccess) {
-      (void)hipGetLastError();
-      HIP_OK(hipMalloc(&d, total));
-    }
-    tmp.d = static_cast<char*>(d);
-    std::vector<char> h(o_qf, 0);
-    memcpy(h.data() + o_task, tasks.data(), tasks.size() * sizeof(LayoutTask));
-    memcpy(h.data() + o_off, t_off.data(), t_off.size() * 4);
-    if (!t_idx.empty()) memcpy(h.data() + o_idx, t_idx.data(), t_idx.size() * 4);
-    PinnedStage::of(current_device()).upload(tmp.d, h.data(), o_qf, st);   // (no wait for the stream)
-    HIP_OK(hipMemsetAsync(tmp.d + o_qf, 0xff, o_kflag - o_qf, st));   // qf = -1, fnfl = ~0
-    HIP_OK(hipMemsetAsync(tmp.d + o_kflag, 0, o_heavy - o_kflag, st));   // kflag, n_heavy
-    AuxWs& ws = AuxWs::of(current_device());
-    std::lock_guard<std::mutex> g(ws.mu);
-    AuxWs::Use use_(ws, st);
-    ws.group(reinterpret_cast<const int64_t*>(fid_offset), n_fid, st);
-    LayoutLists X{};
-    X.tasks = reinterpret_cast<const LayoutTask*>(tmp.d + o_task);
-    X.nfl_task_off = reinterpret_cast<const uint32_t*>(tmp.d + o_off);
-    X.nfl_tasks = reinterpret_cast<const uint32_t*>(tmp.d + o_idx);
-    X.qf = reinterpret_cast<int32_t*>(tmp.d + o_qf);
-    X.qseq = reinterpret_cast<uint32_t*>(tmp.d + o_qseq);
-    X.fnfl = reinterpret_cast<uint32_t*>(tmp.d + o_fnfl);
-    X.ukeys = ws.uids.p;
-    X.nu = ws.nu.p;
-    X.seg_off = ws.seg_off.p;
-    X.seg_pos = ws.seg_pos.p;
-    X.inverse = ws.inverse.p;
-    X.kflag = reinterpret_cast<uint32_t*>(tmp.d + o_kflag);
-    X.n_heavy = reinterpret_cast<uint32_t*>(tmp.d + o_nheavy);
-    X.heavy = reinterpret_cast<uint32_t*>(tmp.d + o_heavy);
-    X.cpos = reinterpret_cast<uint32_t*>(tmp.d + o_cpos);
-    const int64_t inst = int64_t(n_nfl) * batch;
-    if (inst > 0) layout_qmap_kernel<<<dim3(uint32_t((inst + 255) / 256)), 256, 0, st>>>(A, X);
-    layout_heavy_select_kernel<<<dim3(uint32_t((n_fid + 255) / 256)), 256, 0, st>>>(A, X);
-    layout_grad_lists_kernel<<<dim3(uint32_t((n_fid * 16 + 255) / 256)), 256, 0, st>>>(A, X);
-    // (heavy rows: persistent workgroups over the list the select kernel made; rows are disjoint
-    // from the light ones, so the two launches' order does not matter)
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess || cus <= 0)
-      cus = 256;
-    layout_grad_heavy_kernel<<<dim3(uint32_t(std::min<int64_t>(2 * cus, n_fid / kLayoutLight + 64))),
-                               1024, 0, st>>>(A, X);
-    HIP_OK(hipGetLastError());
-    return;
-  }
-  int32_t k = 0;
-  bool addn_open = false;   // the previous launch ended inside an ADDN layout: its next slices add on
-  while (k < n_slices) {
-    // one launch per kMaxLayoutTasks slices.  An ADDN layout's slices are added in configuration
-    // order by one lane group; a layout with more slices than a launch holds continues in the next
-    // launch, which starts from the sums the previous one stored (same order, same roundings).
-    int32_t nt = 0, nu = 0;
-    while (k < n_slices) {
-      int32_t span = 1;
-      if (slices[k].out_type == 2)
-        while (k + span < n_slices && slices[k + span].out_type == 2 &&
-               slices[k + span].out_index == slices[k].out_index) ++span;
-      const bool cont = addn_open;
-      // (forward) a slice that writes floats an earlier slice of this launch writes too starts the next
-      // launch: launches run in stream order, so the later slice's values stay, as in the op's own loop
-      // (inside one launch the two stores come from different lanes or workgroups, in no order)
-      bool clash = false;
-      for (int32_t q = 0; forward && !clash && q < nt; ++q) {
-        const LayoutTask& t = A.task[q];
-        const mhte_layout_slice& sc = slices[k];
-        if (t.out_index != sc.out_index) continue;
-        const int64_t w0 = int64_t(t.dim) * (t.pooling == kPoolFirstN ? std::max(1, t.max_seq) : 1),
-                      w1 = int64_t(sc.dim) * (sc.pooling == kPoolFirstN ? std::max(1, sc.max_sequence_length) : 1);
-        clash = t.out_stride != sc.out_row_floats ||
-                (int64_t(sc.out_offset) < t.out_offset + w0 && int64_t(t.out_offset) < sc.out_offset + w1);
-      }
-      if (clash) break;
-      if (span > kMaxLayoutTasks) {
-        if (nt > 0) break;             // (a long ADDN layout starts its own launch)
-        span = kMaxLayoutTasks;
-        addn_open = true;
-      } else {
-        if (nt + span > kMaxLayoutTasks) break;
-        addn_open = false;
-      }
-      for (int32_t q = 0; q < span; ++q) {
-        check_slice(k + q, k);
-        A.task[nt + q] = task_of(slices[k + q]);
-      }
-      A.unit[nu].first = uint16_t(nt);
-      A.unit[nu].count = uint16_t(span);
-      A.unit[nu].addn = slices[k].out_type == 2 ? (cont ? 2 : 1) : 0;
-      ++nu;
-      nt += span;
-      k += span;
-    }
-    // (the zero runs of outputs this launch writes in full: slices like any other)
-    const bool whole_rows = !zero_runs.empty() || std::find(out_written.begin(), out_written.end(), 1) != out_written.end();
-    if (whole_rows) {
-      for (auto& z : zero_runs) {
-        A.task[nt] = z;
-        A.unit[nu].first = uint16_t(nt);
-        A.unit[nu].count = 1;
-        A.unit[nu].addn = 0;
-        ++nu;
-        ++nt;
-      }
-      // (one bit per output; whole rows are decided without pointer tables only: at most kMaxLayoutOut outputs)
-      uint32_t mask = 0;
-      for (size_t o = 0; o < out_written.size() && o < 32; ++o)
-        if (out_written[o]) mask |= 1u << o;
-      A.zero_missing = int32_t(mask);
-    }
-    A.n_units = nu;
-    const dim3 grid(uint32_t((int64_t(batch) * 16 + 255) / 256), uint32_t(nu));
-    // one fid per feature instance (asserted by the caller), copies of float4-aligned slices: the
-    // vector copy form, plain stores for the gradient
-    bool fast = copy_form;
-    for (int32_t q = 0; fast && q < nt; ++q) {
-      const LayoutTask& t = A.task[q];
-      fast = t.pooling != kPoolFirstN && ((t.start | t.dim | t.out_offset | t.out_stride) & 3) == 0 &&
-             aligned16(outputs[t.out_index]);
-    }
-    for (int32_t q = 0; fast && q < nu; ++q) fast = A.unit[q].count == 1;
-    for (int32_t i = 0; fast && i < n_emb; ++i) fast = (emb_stride[i] & 3) == 0 && aligned16(embeddings[i]);
-    // ... a workgroup per 16 batch rows over all slices of the launch when a row's float4 columns fit its
-    // column table (layout_rows_kernel; MHTE_LAYOUT_ROWS=0: a lane group per (slice, row), round 2's form)
-    int64_t cols = 0;
-    for (int32_t q = 0; q < nu; ++q) cols += A.task[A.unit[q].first].dim / 4;
-    if (fast && rows_form && cols > 0 && cols <= kLayoutRowsMaxF) {
-      const dim3 rgrid(uint32_t((int64_t(batch) + kLayoutRowsR - 1) / kLayoutRowsR));
-      if (forward) layout_rows_kernel<true><<<rgrid, 256, 0, st>>>(A);
-      else layout_rows_kernel<false><<<rgrid, 256, 0, st>>>(A);
-    } else if (whole_rows) {
-      throw Error(MHTE_INTERNAL, "layout: the launch that was to write whole output rows cannot run");
-    } else if (fast) {
-      if (forward) layout_copy_kernel<true><<<grid, 256, 0, st>>>(A);
-      else layout_copy_kernel<false><<<grid, 256, 0, st>>>(A);
-    } else {
-      if (forward) layout_kernel<true><<<grid, 256, 0, st>>>(A);
-      else layout_kernel<false><<<grid, 256, 0, st>>>(A);
-    }
-    HIP_OK(hipGetLastError());
-  }
-}
-}  // namespace mhte
-}  // extern "C++"
-
+// ---- fused_embedding_to_layout (csrc/mhte_layout_plan.h, mhte_layout_kernels.h, mhte_layout_host.h) ------
 mhte_status mhte_embedding_to_layout(const float* const* embeddings, const int32_t* emb_row_floats,
                                      const int64_t* emb_len, int32_t n_emb, const uint64_t* fid_offset,
                                      int64_t n_fid, const int32_t* feature_offset, int64_t n_feature,
@@ -4441,7 +4045,7 @@ mhte_status mhte_embedding_to_layout(const float* const* embeddings, const int32
                                      float* const* outputs, const int64_t* output_len, int32_t n_outputs,
                                      int32_t flags, void* stream) {
   return guard([&] {
-    layout_launch(true, embeddings, emb_row_floats, emb_len, n_emb,
+    embedding_to_layout(true, embeddings, emb_row_floats, emb_len, n_emb,
                   reinterpret_cast<const unsigned long long*>(fid_offset), n_fid, feature_offset, n_feature,
                   nfl_offset, n_nfl, batch_size, slices, n_slices, outputs, output_len, n_outputs, flags,
                   S(stream));
@@ -4456,7 +4060,7 @@ mhte_status mhte_embedding_to_layout_grad(float* const* embeddings_grad, const i
                                           const float* const* tensors_grad, const int64_t* tensor_len,
                                           int32_t n_tensors, int32_t flags, void* stream) {
   return guard([&] {
-    layout_launch(false, const_cast<const float* const*>(embeddings_grad), emb_row_floats, emb_len, n_emb,
+    embedding_to_layout(false, const_cast<const float* const*>(embeddings_grad), emb_row_floats, emb_len, n_emb,
                   reinterpret_cast<const unsigned long long*>(fid_offset), n_fid, feature_offset, n_feature,
                   nfl_offset, n_nfl, batch_size, slices, n_slices,
                   (float* const*)tensors_grad,

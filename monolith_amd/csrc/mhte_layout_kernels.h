@@ -16,30 +16,10 @@
 #define MHTE_LAYOUT_KERNELS_H_
 
 #include "mhte_kernels.h"
+#include "mhte_layout_plan.h"   // LayoutTask, LayoutUnit, the pooling codes and the launch limits
 
 namespace mhte {
 
-constexpr int kMaxLayoutTasks = 48;   // slices per launch (more: several launches)
-constexpr int kMaxLayoutEmb = 64;     // embedding matrices (shard x sub-table) carried in the kernel
-constexpr int kMaxLayoutOut = 32;     // arguments, output tensors likewise; more (the reference's own
-                                      // test has ~1000 and 153): pointer tables in device memory
-
-enum LayoutPooling : int32_t { kPoolSum = 0, kPoolMean = 1, kPoolFirstN = 3 };  // example.proto:176-180
-constexpr int32_t kPoolZeroFill = 100;   // (internal) a run of output columns no slice writes: layout_rows_kernel zeroes it
-
-struct LayoutTask {
-  int32_t nfl_idx;       // SliceConfig.feature_idx
-  int32_t start, dim;    // slice [start, start + dim) of the feature's embedding
-  int32_t pooling;
-  int32_t max_seq;       // FIRSTN: rows kept
-  int32_t out_index;     // which output tensor
-  int32_t out_offset;    // float offset of the slice inside an output row
-  int32_t out_stride;    // floats per output row
-};
-struct LayoutUnit {
-  uint16_t first, count; // tasks [first, first + count); count > 1 only for an ADDN layout
-  uint16_t addn, pad;    // addn: 1 an ADDN layout, 2 its continuation in a following launch
-};
 struct LayoutArgs {
   const float* emb[kMaxLayoutEmb];      // forward: embeddings; backward: gradient buffers (written)
   uint32_t emb_stride[kMaxLayoutEmb];   // floats per row (PtrWrapper.offset)
@@ -167,8 +147,6 @@ __global__ __launch_bounds__(256) void layout_copy_kernel(LayoutArgs A) {
 // addresses into LDS — then walks the float4 columns of its output rows flat, consecutive lanes on
 // consecutive columns across slice boundaries: whole 128-byte lines of a CONCAT row leave one workgroup,
 // every lane moves 16 bytes, kLayoutRowsUnroll independent loads in flight per lane.
-constexpr int kLayoutRowsR = 16;
-constexpr int kLayoutRowsMaxF = 2048;   // float4 columns of one batch row over the launch's slices
 constexpr int kLayoutRowsUnroll = 8;
 template <bool FORWARD>
 __global__ __launch_bounds__(256) void layout_rows_kernel(LayoutArgs A) {
