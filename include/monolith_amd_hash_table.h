@@ -660,6 +660,47 @@ mhte_status mhte_feature_insight_plan(int64_t batch, int64_t in_cols, int32_t k,
                                       int32_t n);
 mhte_status mhte_feature_insight_launch_counts(int64_t* out, int32_t n);
 
+/* ---- the CIN layer (csrc/mhte_cin_core.h, mhte_cin_kernels.h, mhte_cin_host.h) -----------------------------
+ * One layer of the compressed interaction network of xDeepFM (NT/layers/feature_cross.py:694-794) and its
+ * gradients: a 1x1 convolution over the outer product of the running state with the input, which the reference
+ * materialises as [B, D, H m] and these kernels form in registers only.
+ * x0 [dev f32, B x m x D] as the layer's input is given, xl [dev f32, B x H x D] (the state, feature-major: the
+ * first layer passes x0 itself with H == m), w [dev f32, H m x U] with the channel index h m + j, bias [dev f32, U]:
+ *   out[b, d, u]  = act( sum_{h, j} xl[b, h, d] * x0[b, j, d] * w[h m + j, u] + bias[u] )
+ *   xnext[b, u, d] = out[b, d, u]                                             [B x U x D], the next layer's xl
+ *   pooled[b, u]  = sum_d out[b, d, u]                                        [B x U]
+ * activation: 0 identity, 1 relu.  With g = (dxnext + dpooled) * act'(out), relu's mask read from xnext > 0:
+ *   dxl[b, h, d]  = sum_{j, u} g w[h m + j, u] x0[b, j, d]      dx0[b, j, d] = sum_{h, u} g w[h m + j, u] xl[b, h, d]
+ *   dw[h m + j, u] = sum_{b, d} xl[b, h, d] x0[b, j, d] g       dbias[u]     = sum_{b, d} g
+ * Everything is fp32 and every product v_mfma_f32_32x32x2_f32; no atomics; the order of every sum is a function of
+ * the shape alone: the same bits on every run, and whichever gradients are asked for.  Every zero written by a
+ * gradient is +0.
+ *   mhte_cin_layer:       xnext may be NULL (a last layer: its [B x U x D] is never written).  B == 0: no launch.
+ *   mhte_cin_layer_grad:  dxnext may be NULL (a last layer); xnext is read with relu only; dx0, dxl, dw, dbias:
+ *                         any may be NULL, not all.  B == 0: dw and dbias are cleared to +0, nothing else.
+ *   mhte_cin_plan:        n must be 6: out = row block of the forward, column tiles per wavefront, K rows per
+ *                         chunk, rows per slab of the weight gradient, slabs, workspace bytes
+ *                         (slabs * (H m + 1) * U * 4 for more than one slab, else 0).  Needs no device, a function
+ *                         of (B, m, D, H, U) alone.
+ *   mhte_cin_launch_counts: the launches of this process by kernel form, n must be 5: 0 forward with xnext,
+ *                         1 forward without, 2 input gradients, 3 weight and bias gradient, 4 slab sum.
+ * Launches per call: one (forward); one for dx0 and / or dxl, one for dw and / or dbias, plus the slab sum when the
+ * plan has more than one slab.  No entry point waits for the device, reads a device value or allocates beyond the
+ * first growth of the per-device workspace (the slab partials), so a call can be captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand, a pointer that is not 4-byte aligned, m outside [1, 64], D
+ * outside [1, 128], H or U outside [1, 512], B < 0 or B * D beyond 2^30, an activation that is neither 0 nor 1, a
+ * grad entry with every output NULL, relu in a grad entry without xnext. */
+mhte_status mhte_cin_layer(const float* x0, const float* xl, const float* w, const float* bias, int64_t B, int32_t m,
+                           int32_t D, int32_t H, int32_t U, int32_t activation, float* xnext, float* pooled,
+                           void* stream);
+mhte_status mhte_cin_layer_grad(const float* dxnext, const float* dpooled, const float* x0, const float* xl,
+                                const float* w, const float* xnext, int64_t B, int32_t m, int32_t D, int32_t H,
+                                int32_t U, int32_t activation, float* dx0, float* dxl, float* dw, float* dbias,
+                                void* stream);
+mhte_status mhte_cin_plan(int64_t B, int32_t m, int32_t D, int32_t H, int32_t U, int64_t* out, int32_t n);
+mhte_status mhte_cin_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

@@ -45,6 +45,7 @@
 #include "mhte_auc_kernels.h"
 #include "mhte_bsm_kernels.h"
 #include "mhte_fi_kernels.h"
+#include "mhte_cin_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -1972,6 +1973,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_auc_host.h"
 #include "mhte_bsm_host.h"
 #include "mhte_fi_host.h"
+#include "mhte_cin_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 #include "mhte_layout_host.h"
@@ -2791,6 +2793,35 @@ mhte_status mhte_feature_insight_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kFiCounters) arg_bad(op, "n must be " + std::to_string(kFiCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kFiCounters; ++i) out[i] = g_fi_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- the CIN layer (csrc/mhte_cin_core.h, mhte_cin_kernels.h, mhte_cin_host.h) ---------------------------
+mhte_status mhte_cin_layer(const float* x0, const float* xl, const float* w, const float* bias, int64_t B, int32_t m,
+                           int32_t D, int32_t H, int32_t U, int32_t activation, float* xnext, float* pooled,
+                           void* stream) {
+  return guard([&] { cin_forward(x0, xl, w, bias, B, m, D, H, U, activation, xnext, pooled, stream); });
+}
+
+mhte_status mhte_cin_layer_grad(const float* dxnext, const float* dpooled, const float* x0, const float* xl,
+                                const float* w, const float* xnext, int64_t B, int32_t m, int32_t D, int32_t H,
+                                int32_t U, int32_t activation, float* dx0, float* dxl, float* dw, float* dbias,
+                                void* stream) {
+  return guard([&] {
+    cin_gradient(dxnext, dpooled, x0, xl, w, xnext, B, m, D, H, U, activation, dx0, dxl, dw, dbias, stream);
+  });
+}
+
+mhte_status mhte_cin_plan(int64_t B, int32_t m, int32_t D, int32_t H, int32_t U, int64_t* out, int32_t n) {
+  return guard([&] { cin_plan_out(B, m, D, H, U, out, n); });
+}
+
+mhte_status mhte_cin_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "cin_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kCinCounters) arg_bad(op, "n must be " + std::to_string(kCinCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kCinCounters; ++i) out[i] = g_cin_launches[i].load(std::memory_order_relaxed);
   });
 }
 

@@ -25,6 +25,7 @@ struct AuxWs {
   DevBuf<char> auc;                   // in-batch AUC loss (mhte_auc_host.h): the plan's arrays, by its offsets
   DevBuf<char> bsm;                   // batch softmax loss (mhte_bsm_host.h): the same
   DevBuf<char> fi;                    // FeatureInsight (mhte_fi_host.h): the slab partials of the weight gradient
+  DevBuf<char> cin;                   // the CIN layer (mhte_cin_host.h): the slab partials of dw and dbias
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;

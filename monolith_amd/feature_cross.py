@@ -1,14 +1,18 @@
 """Feature-cross layers on MI355X — host-side mirror of monolith/native_training/layers/feature_cross.py.
 
-Only ``GroupInt`` (alias ``FFM``, reference :69-146) lives here: the layer between the per-feature outputs of the
-layout op and the dense tower.  Its cross is ``layer_ops.ffm``, one hand-written launch forward and one backward.
-The attention variant (``use_attention=True``: an MLP over the stacked products) is not built.
+``GroupInt`` (alias ``FFM``, reference :69-146) is the layer between the per-feature outputs of the layout op and
+the dense tower.  Its cross is ``layer_ops.ffm``, one hand-written launch forward and one backward.  The attention
+variant (``use_attention=True``: an MLP over the stacked products) is not built.
+
+``CIN`` (reference :694-794) is xDeepFM's compressed interaction network over ``layer_ops.cin_layer``: one fused
+fp32 MFMA launch per layer forward, two or three backward, without the reference's ``[B, D, H m]`` intermediate.
+``AllInt``, ``CDot``, ``CAN`` and ``DCN`` are not built.
 """
 from typing import List, Sequence
 
 import torch
 
-from monolith_amd.layer_ops import INT_TYPES, ffm
+from monolith_amd.layer_ops import CIN_ACTIVATIONS, INT_TYPES, cin_layer, ffm
 
 
 class GroupInt(torch.nn.Module):
@@ -61,3 +65,66 @@ class GroupInt(torch.nn.Module):
 
 
 FFM = GroupInt
+
+
+class CIN(torch.nn.Module):
+  """Compressed Interaction Network, the explicit high-order cross of xDeepFM (reference :694-794).
+
+  Layer i is a 1x1 convolution over the outer product of the running state ``[B, H_i, D]`` with the input
+  ``[B, m, D]`` (``H_0 = m``, ``H_i = hidden_uints[i - 1]``); every layer's output is summed over ``D`` and the sums
+  are concatenated.  Each layer is one launch of ``layer_ops.cin_layer``; the last one has no activation and never
+  writes its ``[B, U, D]`` output.
+
+  Args:
+    hidden_uints: the filters of each layer (the reference's spelling, so that configs carry over).
+    activation: None or ``'relu'``, applied on every layer but the last.
+    initializer: ``'glorot_uniform'`` (the only one built).
+    regularizer: kept for the config, not applied.
+
+  Input ``[B, m, D]`` -> ``[B, sum(hidden_uints)]``.  Parameters ``kernel_i`` ``[H_i m, U_i]`` and ``bias_i``
+  ``[U_i]`` are created from the first input's shape.
+  """
+
+  def __init__(self, hidden_uints: Sequence[int], activation=None, initializer="glorot_uniform", regularizer=None):
+    super().__init__()
+    if activation not in CIN_ACTIVATIONS:
+      raise NotImplementedError("CIN: activation must be None or 'relu', got %r" % (activation,))
+    if initializer != "glorot_uniform":
+      raise NotImplementedError("CIN: initializer must be 'glorot_uniform', got %r" % (initializer,))
+    self.hidden_uints = [int(u) for u in hidden_uints]
+    if not self.hidden_uints or min(self.hidden_uints) < 1:
+      raise ValueError("CIN: hidden_uints must hold at least one int >= 1, got %r" % (hidden_uints,))
+    self.activation = activation
+    self.initializer = initializer
+    self.regularizer = regularizer
+    self._built_for = None
+
+  def _build(self, x: torch.Tensor):
+    m = int(x.shape[1])
+    for i, units in enumerate(self.hidden_uints):
+      fan_in = (m if i == 0 else self.hidden_uints[i - 1]) * m
+      limit = (6.0 / (fan_in + units)) ** 0.5   # glorot uniform of Conv1D's (1, H m, U) kernel
+      kernel = torch.empty((fan_in, units), dtype=torch.float32, device=x.device).uniform_(-limit, limit)
+      self.register_parameter("kernel_%d" % i, torch.nn.Parameter(kernel))
+      self.register_parameter("bias_%d" % i, torch.nn.Parameter(torch.zeros(units, dtype=torch.float32,
+                                                                            device=x.device)))
+    self._built_for = (m, int(x.shape[2]))
+
+  def forward(self, inputs: torch.Tensor):
+    if not isinstance(inputs, torch.Tensor) or inputs.dim() != 3:
+      raise ValueError("CIN: the input must be a [B, m, D] tensor")
+    if self._built_for is None:
+      self._build(inputs)
+    if self._built_for != (int(inputs.shape[1]), int(inputs.shape[2])):
+      raise ValueError("CIN: built for [B, %d, %d], got %s" % (self._built_for + (tuple(inputs.shape),)))
+    xl, pooled = inputs, []
+    last = len(self.hidden_uints) - 1
+    for i in range(last + 1):
+      xl, p = cin_layer(inputs, xl, getattr(self, "kernel_%d" % i), getattr(self, "bias_%d" % i),
+                        None if i == last else self.activation, want_next=i != last)
+      pooled.append(p)
+    return torch.cat(pooled, dim=1)
+
+  def get_config(self):
+    return {"hidden_uints": self.hidden_uints, "activation": self.activation, "initializer": self.initializer,
+            "regularizer": self.regularizer}

@@ -15,7 +15,11 @@ block per feature (``segment_sizes``), ``[B, F K]``; its gradient ``feature_insi
 ``[B, F K]`` intermediate.  They sit behind ``mhte_feature_insight`` / ``mhte_feature_insight_grad``
 (csrc/mhte_fi_kernels.h): exact fp32 ``fmaf`` chains in a fixed order, no atomics, the same bits on every run.
 
-Tensors are 2-D float32 on the GPU; a tensor that is not contiguous is copied first.
+``cin_layer`` is one layer of the compressed interaction network (feature_cross.py:694-794, ``feature_cross.CIN``)
+behind ``mhte_cin_layer`` / ``mhte_cin_layer_grad`` (csrc/mhte_cin_kernels.h): fp32 MFMA GEMMs whose A operand, the
+reference's ``[B, D, H m]`` outer product, is formed in registers and never stored.
+
+Tensors are float32 on the GPU; a tensor that is not contiguous is copied first.
 """
 import ctypes as C
 from typing import Optional, Sequence, Tuple
@@ -265,3 +269,146 @@ def feature_insight_launch_counts():
   out = (C.c_int64 * len(FI_COUNTER_NAMES))()
   check(_lib.lib().mhte_feature_insight_launch_counts(out, len(FI_COUNTER_NAMES)))
   return dict(zip(FI_COUNTER_NAMES, [int(x) for x in out]))
+
+
+# ---- the CIN layer (feature_cross.py:694-794) -------------------------------------------------------------------
+CIN_ACTIVATIONS = (None, "relu")   # the index is the ABI's activation
+# mhte_cin_launch_counts' order
+CIN_COUNTER_NAMES = ("forward", "forward_last", "input_grad", "weight_grad", "slab_sum")
+# mhte_cin_plan's order
+CIN_PLAN_NAMES = ("row_block", "column_tiles", "k_chunk", "slab_rows", "slabs", "workspace_bytes")
+
+
+def _cin_activation(what, activation) -> int:
+  if activation not in CIN_ACTIVATIONS:
+    raise NotImplementedError("%s: activation must be None or 'relu', got %r" % (what, activation))
+  return CIN_ACTIVATIONS.index(activation)
+
+
+def _cin_operands(what, shapes, **tensors):
+  """Checked and contiguous, in the order given; ``shapes``: {name: the shape it must have}; None is passed on."""
+  out = []
+  first = None
+  for name, t in tensors.items():
+    if t is None:
+      out.append(None)
+      continue
+    if not isinstance(t, torch.Tensor):
+      raise TypeError("%s: %s must be a torch tensor, got %s" % (what, name, type(t).__name__))
+    if t.dtype != torch.float32:
+      raise TypeError("%s: %s must be float32, got %s" % (what, name, t.dtype))
+    if first is None:
+      first = (name, t)
+    elif t.device != first[1].device:
+      raise ValueError("%s: %s is on %s, %s on %s" % (what, name, t.device, first[0], first[1].device))
+    if name in shapes and tuple(t.shape) != tuple(shapes[name]):
+      raise ValueError("%s: %s must have the shape %s, got %s" % (what, name, tuple(shapes[name]), tuple(t.shape)))
+    out.append(t)
+  for name, t in tensors.items():
+    if t is not None and not t.is_cuda:
+      raise TypeError("%s: %s must be on the GPU (there is no CPU path)" % (what, name))
+  return [t if t is None or t.is_contiguous() else t.contiguous() for t in out]
+
+
+def _cin_dims(what, x0, xl, weight):
+  for name, t, nd in (("x0", x0, 3), ("xl", xl, 3), ("weight", weight, 2)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError("%s: %s must be a torch tensor, got %s" % (what, name, type(t).__name__))
+    if t.dim() != nd:
+      raise ValueError("%s: %s is not %dD (shape %s)" % (what, name, nd, tuple(t.shape)))
+  B, m, D = x0.shape
+  H, U = xl.shape[1], weight.shape[1]
+  return B, m, D, H, U, {"xl": (B, H, D), "weight": (H * m, U), "bias": (U,), "xnext": (B, U, D),
+                         "dxnext": (B, U, D), "dpooled": (B, U)}
+
+
+def _cin_forward(x0, xl, weight, bias, activation, want_next):
+  what = "cin_layer"
+  act = _cin_activation(what, activation)
+  B, m, D, H, U, shapes = _cin_dims(what, x0, xl, weight)
+  x0, xl, weight, bias = _cin_operands(what, shapes, x0=x0, xl=xl, weight=weight, bias=bias)
+  xnext = torch.empty((B, U, D), dtype=torch.float32, device=x0.device) if want_next else None
+  pooled = torch.empty((B, U), dtype=torch.float32, device=x0.device)
+  with torch.cuda.device(x0.device):
+    check(_lib.lib().mhte_cin_layer(vp(x0), vp(xl), vp(weight), vp(bias), B, m, D, H, U, act, vp(xnext), vp(pooled),
+                                    _stream()))
+  return xnext, pooled, (x0, xl, weight)
+
+
+def cin_layer_grad(dxnext: Optional[torch.Tensor], dpooled: torch.Tensor, x0: torch.Tensor, xl: torch.Tensor,
+                   weight: torch.Tensor, xnext: Optional[torch.Tensor], activation=None, want_x0: bool = True,
+                   want_xl: bool = True, want_weight: bool = True, want_bias: bool = True):
+  """-> (dx0, dxl, dweight, dbias) of ``cin_layer``, shaped like their operands.  ``dxnext`` is None for a layer
+  whose ``xnext`` was not used; ``xnext`` (the layer's saved output) is needed with ``'relu'`` only.  A gradient
+  that is not wanted is ``None``; asking for one alone gives the same bits as asking for all."""
+  what = "cin_layer_grad"
+  act = _cin_activation(what, activation)
+  if not (want_x0 or want_xl or want_weight or want_bias):
+    raise ValueError("%s: at least one of want_x0, want_xl, want_weight and want_bias" % what)
+  if act and xnext is None:
+    raise ValueError("%s: 'relu' needs xnext, the layer's saved output" % what)
+  B, m, D, H, U, shapes = _cin_dims(what, x0, xl, weight)
+  dxnext, dpooled, x0, xl, weight, xnext = _cin_operands(what, shapes, dxnext=dxnext, dpooled=dpooled, x0=x0, xl=xl,
+                                                         weight=weight, xnext=xnext)
+  dx0 = torch.empty_like(x0) if want_x0 else None
+  dxl = torch.empty_like(xl) if want_xl else None
+  dweight = torch.empty_like(weight) if want_weight else None
+  dbias = torch.empty((U,), dtype=torch.float32, device=x0.device) if want_bias else None
+  with torch.cuda.device(x0.device):
+    check(_lib.lib().mhte_cin_layer_grad(vp(dxnext), vp(dpooled), vp(x0), vp(xl), vp(weight), vp(xnext), B, m, D, H,
+                                         U, act, vp(dx0), vp(dxl), vp(dweight), vp(dbias), _stream()))
+  return dx0, dxl, dweight, dbias
+
+
+class _CinLayer(torch.autograd.Function):
+  """One layer of CIN.call (feature_cross.py:786-792) with the gradient of its own inputs."""
+
+  @staticmethod
+  def forward(ctx, x0, xl, weight, bias, activation, want_next):
+    # relu's mask is read from the layer's output: a differentiated relu layer keeps it even when it is not returned
+    keep = want_next or (activation is not None and any(ctx.needs_input_grad[:4]))
+    xnext, pooled, (x0_c, xl_c, w_c) = _cin_forward(x0, xl, weight, bias, activation, keep)
+    ctx.save_for_backward(x0_c, xl_c, w_c, *((xnext,) if keep else ()))
+    ctx.activation, ctx.want_next = activation, want_next
+    return (xnext, pooled) if want_next else pooled
+
+  @staticmethod
+  def backward(ctx, *grads):
+    x0, xl, w = ctx.saved_tensors[:3]
+    xnext = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+    dxnext, dpooled = grads if ctx.want_next else (None, grads[0])
+    if dpooled is None:
+      dpooled = torch.zeros((x0.shape[0], w.shape[1]), dtype=torch.float32, device=x0.device)
+    need = ctx.needs_input_grad[:4]
+    if not any(need):
+      return (None,) * 6
+    return cin_layer_grad(dxnext, dpooled, x0, xl, w, xnext, ctx.activation, *need) + (None, None)
+
+
+def cin_layer(x0: torch.Tensor, xl: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, activation=None,
+              want_next: bool = True) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+  """One CIN layer (feature_cross.py:786-794).  ``x0`` ``[B, m, D]``, ``xl`` ``[B, H, D]`` (the first layer passes
+  ``x0``), ``weight`` ``[H m, U]`` with the channel index ``h m + j``, ``bias`` ``[U]`` -> ``(xnext, pooled)``:
+  ``xnext`` ``[B, U, D]``, the next layer's ``xl`` (None with ``want_next=False``: a last layer never writes it), and
+  ``pooled`` ``[B, U]``, the sum over the embedding dimension.  ``activation`` is None or ``'relu'``.
+  Differentiable in ``x0``, ``xl``, ``weight`` and ``bias``.  The ``[B, D, H m]`` outer product of the reference
+  is never stored."""
+  _cin_activation("cin_layer", activation)
+  if want_next:
+    return _CinLayer.apply(x0, xl, weight, bias, activation, True)
+  return None, _CinLayer.apply(x0, xl, weight, bias, activation, False)
+
+
+def cin_plan(B: int, m: int, D: int, H: int, U: int):
+  """{row_block, column_tiles, k_chunk, slab_rows, slabs, workspace_bytes} of a call (mhte_cin_plan): a function of
+  the shape alone, no device needed."""
+  out = (C.c_int64 * len(CIN_PLAN_NAMES))()
+  check(_lib.lib().mhte_cin_plan(int(B), int(m), int(D), int(H), int(U), out, len(CIN_PLAN_NAMES)))
+  return dict(zip(CIN_PLAN_NAMES, [int(x) for x in out]))
+
+
+def cin_launch_counts():
+  """{form: launches of this process} (mhte_cin_launch_counts)."""
+  out = (C.c_int64 * len(CIN_COUNTER_NAMES))()
+  check(_lib.lib().mhte_cin_launch_counts(out, len(CIN_COUNTER_NAMES)))
+  return dict(zip(CIN_COUNTER_NAMES, [int(x) for x in out]))
