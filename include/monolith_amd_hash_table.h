@@ -701,6 +701,51 @@ mhte_status mhte_cin_layer_grad(const float* dxnext, const float* dpooled, const
 mhte_status mhte_cin_plan(int64_t B, int32_t m, int32_t D, int32_t H, int32_t U, int64_t* out, int32_t n);
 mhte_status mhte_cin_launch_counts(int64_t* out, int32_t n);
 
+/* ---- the DCN cross layer (csrc/mhte_dcn_core.h, mhte_dcn_kernels.h, mhte_dcn_host.h) -----------------------
+ * One cross layer of a Deep & Cross network (NT/layers/feature_cross.py:445-690, the Vector and Matrix branches of
+ * DCN.call) and its gradients, each fused around its product.  x0, xl, xnext, dxnext (g below) [dev f32, B x d],
+ * bias [dev f32, d]; type 0 is the vector form with w [dev f32, d], type 1 the matrix form with w [dev f32, d x d],
+ * used as stored (row k contiguous):
+ *   vector:  s[b]   = sum_k xl[b,k] w[k]                xnext = (x0 * s[b] + bias) + xl          aux = s [B]
+ *            ds[b]  = sum_j g[b,j] x0[b,j]              dxl = ds[b] * w + g       dx0 = dx0_acc + g * s[b]
+ *            dw[k]  = sum_b ds[b] xl[b,k]               dbias[j] = sum_b g[b,j]
+ *   matrix:  u[b,j] = sum_k xl[b,k] w[k,j] + bias[j]    xnext = x0 * u + xl                      aux = u [B x d]
+ *            du     = g * x0   (never stored)           dxl = du w^T + g          dx0 = dx0_acc + g * u
+ *            dw[k,j] = sum_b xl[b,k] du[b,j]            dbias[j] = sum_b du[b,j]
+ * Everything is fp32; every product of the matrix form is v_mfma_f32_32x32x2_f32, the vector form is a row dot
+ * reduced across lanes; no atomics; the order of every sum is a function of the shape alone: the same bits on every
+ * run, and whichever gradients are asked for.  Every zero written is +0.
+ *   mhte_dcn_layer:       aux may be NULL (inference: s / u is never written).  B == 0: no launch.
+ *   mhte_dcn_layer_grad:  aux is what the forward wrote, needed when dx0 is asked for.  dx0_acc may be NULL (nothing
+ *                         to add to) or dx0 itself: a stack carries one buffer through its layers.  first != 0 is
+ *                         the stack's first layer, whose xl is x0: dx0 = dx0_acc + g * aux + dxl and dxl is not
+ *                         written.  dx0, dxl, dw, dbias: any may be NULL, not all.  B == 0: dw and dbias are cleared
+ *                         to +0, nothing else.
+ *   mhte_dcn_plan:        n must be 6: out = row block of the forward, column span (matrix: the columns of a
+ *                         workgroup; vector: the columns a kernel instance holds in registers), K rows per chunk
+ *                         (matrix: 32; vector: the 64 lanes of a dot), rows per slab of the weight gradient, slabs,
+ *                         workspace bytes (more than one slab: slabs * (d + 1) * d * 4 matrix, slabs * 2 * d * 4
+ *                         vector; else 0).  Needs no device, a function of (B, d, type) alone.
+ *   mhte_dcn_launch_counts: the launches of this process by kernel form, n must be 9: matrix 0 forward with aux,
+ *                         1 forward without, 2 input gradient, 3 weight and bias gradient, 4 slab sum; vector
+ *                         5 forward with aux, 6 forward without, 7 gradient (input gradients and the slab partials
+ *                         of dw and dbias in one launch), 8 slab sum.
+ * Launches per call: one (forward); matrix gradient: one for dx0 and / or dxl, one for dw and / or dbias, plus the
+ * slab sum when the plan has more than one slab; vector gradient: one, plus the slab sum.  No entry point waits for
+ * the device, reads a device value or allocates beyond the first growth of the per-device workspace (the slab
+ * partials), so a call can be captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand, a pointer that is not 4-byte aligned, d outside [1, 4096], B < 0
+ * or B * d beyond 2^31, a type that is neither 0 nor 1, a grad entry with every output NULL, dx0 without aux,
+ * first without dx0. */
+mhte_status mhte_dcn_layer(const float* x0, const float* xl, const float* w, const float* bias, int64_t B, int32_t d,
+                           int32_t type, float* xnext, float* aux, void* stream);
+mhte_status mhte_dcn_layer_grad(const float* dxnext, const float* x0, const float* xl, const float* w,
+                                const float* aux, int64_t B, int32_t d, int32_t type, int32_t first,
+                                const float* dx0_acc, float* dx0, float* dxl, float* dw, float* dbias, void* stream);
+mhte_status mhte_dcn_plan(int64_t B, int32_t d, int32_t type, int64_t* out, int32_t n);
+mhte_status mhte_dcn_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

@@ -46,6 +46,7 @@
 #include "mhte_bsm_kernels.h"
 #include "mhte_fi_kernels.h"
 #include "mhte_cin_kernels.h"
+#include "mhte_dcn_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -1974,6 +1975,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_bsm_host.h"
 #include "mhte_fi_host.h"
 #include "mhte_cin_host.h"
+#include "mhte_dcn_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 #include "mhte_layout_host.h"
@@ -2822,6 +2824,31 @@ mhte_status mhte_cin_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kCinCounters) arg_bad(op, "n must be " + std::to_string(kCinCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kCinCounters; ++i) out[i] = g_cin_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- the DCN cross layer (csrc/mhte_dcn_core.h, mhte_dcn_kernels.h, mhte_dcn_host.h) ---------------------
+mhte_status mhte_dcn_layer(const float* x0, const float* xl, const float* w, const float* bias, int64_t B, int32_t d,
+                           int32_t type, float* xnext, float* aux, void* stream) {
+  return guard([&] { dcn_forward(x0, xl, w, bias, B, d, type, xnext, aux, stream); });
+}
+
+mhte_status mhte_dcn_layer_grad(const float* dxnext, const float* x0, const float* xl, const float* w,
+                                const float* aux, int64_t B, int32_t d, int32_t type, int32_t first,
+                                const float* dx0_acc, float* dx0, float* dxl, float* dw, float* dbias, void* stream) {
+  return guard([&] { dcn_gradient(dxnext, x0, xl, w, aux, B, d, type, first, dx0_acc, dx0, dxl, dw, dbias, stream); });
+}
+
+mhte_status mhte_dcn_plan(int64_t B, int32_t d, int32_t type, int64_t* out, int32_t n) {
+  return guard([&] { dcn_plan_out(B, d, type, out, n); });
+}
+
+mhte_status mhte_dcn_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "dcn_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kDcnCounters) arg_bad(op, "n must be " + std::to_string(kDcnCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kDcnCounters; ++i) out[i] = g_dcn_launches[i].load(std::memory_order_relaxed);
   });
 }
 

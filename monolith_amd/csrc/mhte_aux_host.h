@@ -26,6 +26,7 @@ struct AuxWs {
   DevBuf<char> bsm;                   // batch softmax loss (mhte_bsm_host.h): the same
   DevBuf<char> fi;                    // FeatureInsight (mhte_fi_host.h): the slab partials of the weight gradient
   DevBuf<char> cin;                   // the CIN layer (mhte_cin_host.h): the slab partials of dw and dbias
+  DevBuf<char> dcn;                   // the DCN cross layer (mhte_dcn_host.h): the same
   static AuxWs& of(int device) {
     static std::mutex m;
     static std::map<int, std::unique_ptr<AuxWs>> all;

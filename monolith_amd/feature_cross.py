@@ -6,13 +6,17 @@ variant (``use_attention=True``: an MLP over the stacked products) is not built.
 
 ``CIN`` (reference :694-794) is xDeepFM's compressed interaction network over ``layer_ops.cin_layer``: one fused
 fp32 MFMA launch per layer forward, two or three backward, without the reference's ``[B, D, H m]`` intermediate.
-``AllInt``, ``CDot``, ``CAN`` and ``DCN`` are not built.
+
+``DCN`` (reference :445-690) is the cross half of a Deep & Cross network, vector and matrix form, over
+``layer_ops.dcn_cross``: one fused launch per layer forward, and the whole stack is one autograd node whose backward
+carries a single ``dx0`` buffer through the layers.  The ``mixed`` form (low-rank experts), kernel norm and dropout
+are not built.  ``AllInt``, ``CDot`` and ``CAN`` are not built.
 """
 from typing import List, Sequence
 
 import torch
 
-from monolith_amd.layer_ops import CIN_ACTIVATIONS, INT_TYPES, cin_layer, ffm
+from monolith_amd.layer_ops import CIN_ACTIVATIONS, DCN_TYPES, INT_TYPES, cin_layer, dcn_cross, ffm
 
 
 class GroupInt(torch.nn.Module):
@@ -128,3 +132,71 @@ class CIN(torch.nn.Module):
   def get_config(self):
     return {"hidden_uints": self.hidden_uints, "activation": self.activation, "initializer": self.initializer,
             "regularizer": self.regularizer}
+
+
+class DCN(torch.nn.Module):
+  """The cross network of Deep & Cross (reference :445-690), ``xl = x0`` and per layer
+
+    vector:  ``xl = x0 * (xl @ kernel_i) + bias_i + xl``      kernel_i ``[d, 1]``
+    matrix:  ``xl = x0 * (xl @ kernel_i + bias_i) + xl``      kernel_i ``[d, d]``
+
+  with ``bias_i`` ``[1, d]``; every layer is one launch of ``layer_ops.dcn_cross``'s kernels.
+
+  Args:
+    layer_num: the number of cross layers.
+    dcn_type: ``'vector'`` or ``'matrix'``; ``'mixed'`` is not built.
+    initializer: None (glorot normal: a normal of stddev ``sqrt(2 / (fan_in + fan_out)) / 0.87962566`` truncated at
+      two stddev); nothing else is built.
+    regularizer, num_experts, low_rank, keep_prob, mode: kept for the config, not applied.
+    allow_kernel_norm, use_dropout: must be False.
+
+  Input ``[B, d]`` -> ``[B, d]``.  Parameters are created from the first input's shape.
+  """
+
+  def __init__(self, layer_num: int = 1, dcn_type: str = "matrix", initializer=None, regularizer=None,
+               num_experts: int = 1, low_rank: int = 0, allow_kernel_norm: bool = False, use_dropout: bool = False,
+               keep_prob: float = 0.95, mode: str = "train"):
+    super().__init__()
+    if dcn_type not in DCN_TYPES:
+      raise NotImplementedError("DCN: dcn_type must be 'vector' or 'matrix', got %r" % (dcn_type,))
+    if allow_kernel_norm:
+      raise NotImplementedError("DCN: allow_kernel_norm=True is not built")
+    if use_dropout:
+      raise NotImplementedError("DCN: use_dropout=True is not built")
+    if initializer is not None:
+      raise NotImplementedError("DCN: initializer must be None (glorot normal), got %r" % (initializer,))
+    if int(layer_num) < 1:
+      raise ValueError("DCN: layer_num must be an int >= 1, got %r" % (layer_num,))
+    self.layer_num, self.dcn_type = int(layer_num), dcn_type
+    self.initializer, self.regularizer = initializer, regularizer
+    self.num_experts, self.low_rank = num_experts, low_rank
+    self.allow_kernel_norm, self.use_dropout, self.keep_prob, self.mode = False, False, keep_prob, mode
+    self._built_for = None
+
+  def _build(self, x: torch.Tensor):
+    d = int(x.shape[1])
+    cols = d if self.dcn_type == "matrix" else 1
+    std = (2.0 / (d + cols)) ** 0.5 / 0.87962566
+    for i in range(self.layer_num):
+      kernel = torch.empty((d, cols), dtype=torch.float32, device=x.device)
+      torch.nn.init.trunc_normal_(kernel, 0.0, std, -2 * std, 2 * std)
+      self.register_parameter("kernel_%d" % i, torch.nn.Parameter(kernel))
+      self.register_parameter("bias_%d" % i, torch.nn.Parameter(torch.zeros((1, d), dtype=torch.float32,
+                                                                            device=x.device)))
+    self._built_for = d
+
+  def forward(self, inputs: torch.Tensor):
+    if not isinstance(inputs, torch.Tensor) or inputs.dim() != 2:
+      raise ValueError("DCN: the input must be a [B, d] tensor")
+    if self._built_for is None:
+      self._build(inputs)
+    if self._built_for != int(inputs.shape[1]):
+      raise ValueError("DCN: built for [B, %d], got %s" % (self._built_for, tuple(inputs.shape)))
+    return dcn_cross(inputs, [getattr(self, "kernel_%d" % i) for i in range(self.layer_num)],
+                     [getattr(self, "bias_%d" % i) for i in range(self.layer_num)], self.dcn_type)
+
+  def get_config(self):
+    return {"layer_num": self.layer_num, "dcn_type": self.dcn_type, "initializer": self.initializer,
+            "regularizer": self.regularizer, "num_experts": self.num_experts, "low_rank": self.low_rank,
+            "allow_kernel_norm": self.allow_kernel_norm, "use_dropout": self.use_dropout,
+            "keep_prob": self.keep_prob, "mode": self.mode}

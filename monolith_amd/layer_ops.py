@@ -19,6 +19,11 @@ block per feature (``segment_sizes``), ``[B, F K]``; its gradient ``feature_insi
 behind ``mhte_cin_layer`` / ``mhte_cin_layer_grad`` (csrc/mhte_cin_kernels.h): fp32 MFMA GEMMs whose A operand, the
 reference's ``[B, D, H m]`` outer product, is formed in registers and never stored.
 
+``dcn_cross`` is the cross stack of a Deep & Cross network (feature_cross.py:445-690, ``feature_cross.DCN``, the
+vector and matrix forms) behind ``mhte_dcn_layer`` / ``mhte_dcn_layer_grad`` (csrc/mhte_dcn_kernels.h): per layer one
+launch whose epilogue does the bias, the multiply by ``x0`` and the residual, and a gradient that carries the stack's
+running ``dx0`` as an operand.
+
 Tensors are float32 on the GPU; a tensor that is not contiguous is copied first.
 """
 import ctypes as C
@@ -412,3 +417,136 @@ def cin_launch_counts():
   out = (C.c_int64 * len(CIN_COUNTER_NAMES))()
   check(_lib.lib().mhte_cin_launch_counts(out, len(CIN_COUNTER_NAMES)))
   return dict(zip(CIN_COUNTER_NAMES, [int(x) for x in out]))
+
+
+# ---- the DCN cross layer (feature_cross.py:445-690) ---------------------------------------------------------------
+DCN_TYPES = ("vector", "matrix")   # the index is the ABI's type; the reference's 'mixed' is not built
+# mhte_dcn_launch_counts' order
+DCN_COUNTER_NAMES = ("matrix_forward", "matrix_forward_no_aux", "matrix_input_grad", "matrix_weight_grad",
+                     "matrix_slab_sum", "vector_forward", "vector_forward_no_aux", "vector_grad", "vector_slab_sum")
+# mhte_dcn_plan's order
+DCN_PLAN_NAMES = ("row_block", "column_span", "k_chunk", "slab_rows", "slabs", "workspace_bytes")
+
+
+def _dcn_type(what, dcn_type) -> int:
+  if dcn_type not in DCN_TYPES:
+    raise NotImplementedError("%s: dcn_type must be 'vector' or 'matrix', got %r" % (what, dcn_type))
+  return DCN_TYPES.index(dcn_type)
+
+
+def _dcn_dims(what, x0, typ):
+  if not isinstance(x0, torch.Tensor):
+    raise TypeError("%s: x0 must be a torch tensor, got %s" % (what, type(x0).__name__))
+  if x0.dim() != 2:
+    raise ValueError("%s: x0 is not 2D (shape %s)" % (what, tuple(x0.shape)))
+  B, d = x0.shape
+  return B, d, {"xl": (B, d), "weight": (d, d) if typ else (d, 1), "bias": (1, d), "dxnext": (B, d),
+                "aux": (B, d) if typ else (B,), "dx0_acc": (B, d)}
+
+
+def dcn_layer(x0: torch.Tensor, xl: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, dcn_type="matrix",
+              want_aux: bool = True):
+  """One DCN cross layer (feature_cross.py:564-568), no autograd: ``x0``, ``xl`` ``[B, d]``, ``weight`` ``[d, 1]``
+  (``'vector'``) or ``[d, d]`` (``'matrix'``), ``bias`` ``[1, d]`` -> ``(xnext, aux)``.  ``aux`` is what
+  ``dcn_layer_grad`` needs of the forward (``s`` ``[B]`` / ``u`` ``[B, d]``); with ``want_aux=False`` it is None and
+  never written.  ``dcn_cross`` is the differentiable stack."""
+  what = "dcn_layer"
+  typ = _dcn_type(what, dcn_type)
+  B, d, shapes = _dcn_dims(what, x0, typ)
+  x0, xl, weight, bias = _cin_operands(what, shapes, x0=x0, xl=xl, weight=weight, bias=bias)
+  xnext = torch.empty_like(x0)
+  aux = torch.empty(shapes["aux"], dtype=torch.float32, device=x0.device) if want_aux else None
+  with torch.cuda.device(x0.device):
+    check(_lib.lib().mhte_dcn_layer(vp(x0), vp(xl), vp(weight), vp(bias), B, d, typ, vp(xnext), vp(aux), _stream()))
+  return xnext, aux
+
+
+def dcn_layer_grad(dxnext: torch.Tensor, x0: torch.Tensor, xl: torch.Tensor, weight: torch.Tensor,
+                   aux: Optional[torch.Tensor], dcn_type="matrix", first: bool = False,
+                   dx0_acc: Optional[torch.Tensor] = None, want_x0: bool = True, want_xl: bool = True,
+                   want_weight: bool = True, want_bias: bool = True):
+  """-> (dx0, dxl, dweight, dbias) of ``dcn_layer``, shaped like their operands.  ``dx0 = dx0_acc + (this layer's
+  part)``; a contiguous ``dx0_acc`` is updated in place and returned as ``dx0``.  ``first=True`` is a stack's first
+  layer, whose ``xl`` is ``x0``: its ``dxl`` is added into ``dx0`` and returned as None.  A gradient that is not wanted
+  is None; asking for one alone gives the same bits as asking for all."""
+  what = "dcn_layer_grad"
+  typ = _dcn_type(what, dcn_type)
+  if not (want_x0 or want_xl or want_weight or want_bias):
+    raise ValueError("%s: at least one of want_x0, want_xl, want_weight and want_bias" % what)
+  if want_x0 and aux is None:
+    raise ValueError("%s: dx0 needs aux, what the forward saved" % what)
+  if first and not want_x0:
+    raise ValueError("%s: first=True needs want_x0 (the layer's input gradient is dx0)" % what)
+  B, d, shapes = _dcn_dims(what, x0, typ)
+  dxnext, x0, xl, weight, aux, dx0_acc = _cin_operands(what, shapes, dxnext=dxnext, x0=x0, xl=xl, weight=weight,
+                                                       aux=aux, dx0_acc=dx0_acc)
+  dx0 = (dx0_acc if dx0_acc is not None else torch.empty_like(x0)) if want_x0 else None
+  dxl = torch.empty_like(x0) if want_xl and not first else None
+  dweight = torch.empty_like(weight) if want_weight else None
+  dbias = torch.empty((1, d), dtype=torch.float32, device=x0.device) if want_bias else None
+  with torch.cuda.device(x0.device):
+    check(_lib.lib().mhte_dcn_layer_grad(vp(dxnext), vp(x0), vp(xl), vp(weight), vp(aux), B, d, typ, int(bool(first)),
+                                         vp(dx0_acc), vp(dx0), vp(dxl), vp(dweight), vp(dbias), _stream()))
+  return dx0, dxl, dweight, dbias
+
+
+class _DcnCross(torch.autograd.Function):
+  """The whole stack of DCN.call (feature_cross.py:560-606) as one node: L forward launches, and backward L input
+  gradient launches from the last layer to the first with one dx0 buffer carried through them."""
+
+  @staticmethod
+  def forward(ctx, x0, dcn_type, n, keep, *params):
+    kernels, biases = params[:n], params[n:]
+    xl, saved = x0, []
+    for w, b in zip(kernels, biases):
+      xnext, aux = dcn_layer(x0, xl, w, b, dcn_type, want_aux=keep)
+      saved += [xl, aux]
+      xl = xnext
+    if keep:
+      ctx.save_for_backward(*kernels, *saved)
+    ctx.dcn_type, ctx.n = dcn_type, n
+    return xl
+
+  @staticmethod
+  def backward(ctx, g):
+    n = ctx.n
+    kernels, saved = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+    x0 = saved[0]
+    dx0, dws, dbs = None, [None] * n, [None] * n
+    for i in reversed(range(n)):
+      dx0, g, dws[i], dbs[i] = dcn_layer_grad(g, x0, saved[2 * i], kernels[i], saved[2 * i + 1], ctx.dcn_type,
+                                              first=i == 0, dx0_acc=dx0)
+    return (dx0, None, None, None) + tuple(dws) + tuple(dbs)
+
+
+def dcn_cross(x0: torch.Tensor, kernels: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+              dcn_type="matrix") -> torch.Tensor:
+  """The cross stack of a Deep & Cross network (feature_cross.py:560-606): ``xl = x0`` and, per layer,
+  ``xl = x0 * (xl @ kernel) + bias + xl`` (``'vector'``, kernel ``[d, 1]``) or ``xl = x0 * (xl @ kernel + bias) + xl``
+  (``'matrix'``, kernel ``[d, d]``), bias ``[1, d]`` -> ``[B, d]``.  Differentiable in ``x0`` and every kernel and
+  bias as ONE autograd node: one launch per layer forward; backward one input-gradient and one weight-gradient
+  launch per layer (the vector form does both in one) plus a slab sum where the plan has several slabs, and no torch
+  arithmetic.  Under ``torch.no_grad()`` nothing is saved or written for a backward."""
+  what = "dcn_cross"
+  _dcn_type(what, dcn_type)
+  kernels, biases = tuple(kernels), tuple(biases)
+  if not kernels or len(kernels) != len(biases):
+    raise ValueError("%s: as many kernels as biases, at least one (got %d and %d)" % (what, len(kernels), len(biases)))
+  keep = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                         for t in (x0,) + kernels + biases)
+  return _DcnCross.apply(x0, dcn_type, len(kernels), keep, *kernels, *biases)
+
+
+def dcn_plan(B: int, d: int, dcn_type="matrix"):
+  """{row_block, column_span, k_chunk, slab_rows, slabs, workspace_bytes} of a call (mhte_dcn_plan): a function of
+  the shape alone, no device needed."""
+  out = (C.c_int64 * len(DCN_PLAN_NAMES))()
+  check(_lib.lib().mhte_dcn_plan(int(B), int(d), _dcn_type("dcn_plan", dcn_type), out, len(DCN_PLAN_NAMES)))
+  return dict(zip(DCN_PLAN_NAMES, [int(x) for x in out]))
+
+
+def dcn_launch_counts():
+  """{form: launches of this process} (mhte_dcn_launch_counts)."""
+  out = (C.c_int64 * len(DCN_COUNTER_NAMES))()
+  check(_lib.lib().mhte_dcn_launch_counts(out, len(DCN_COUNTER_NAMES)))
+  return dict(zip(DCN_COUNTER_NAMES, [int(x) for x in out]))
