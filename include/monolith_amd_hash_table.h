@@ -746,6 +746,39 @@ mhte_status mhte_dcn_layer_grad(const float* dxnext, const float* x0, const floa
 mhte_status mhte_dcn_plan(int64_t B, int32_t d, int32_t type, int64_t* out, int32_t n);
 mhte_status mhte_dcn_launch_counts(int64_t* out, int32_t n);
 
+/* ---- the CAN co-action unit (csrc/mhte_can_core.h, mhte_can_kernels.h, mhte_can_host.h) -------------------
+ * The Co-Action Network's unit (NT/layers/feature_cross.py:345-440, CAN.call in its four input forms): every sample
+ * runs its own small MLP, whose weights are cut out of its item embedding, over its user rows.  user [dev f32,
+ * B x F x T x d] (R = F * T rows per sample; a form without a feature or a sequence axis has F = 1 or T = 1),
+ * item [dev f32, B x P] with P = layer_num * d * (d + 1), out and dout [dev f32, B x F x d]:
+ *   W_i[k][j] = item[b, i*d*(d+1) + k*d + j]       b_i[j] = item[b, i*d*(d+1) + d*d + j]
+ *   h_0 = user[b]       h_{i+1} = act(h_i W_i + b_i)  on every layer       out[b, f] = sum_t h_L[f*T + t]
+ *   mhte_can_forward  replaces :386-430 (the split of item, layer_num batched matmuls with their bias and activation
+ *                     passes, the reduce_sum over T): one launch, no intermediate reaches memory.  B == 0: no launch.
+ *   mhte_can_grad     replaces the autograd backward of those lines: one launch that recomputes h_1 .. h_L per row
+ *                     tile in registers (the forward saves nothing) and writes duser (shaped like user) and ditem
+ *                     [B x P] ((dW_i, db_i) where item holds (W_i, b_i)).  duser, ditem: either may be NULL, not
+ *                     both; a gradient asked for alone has the bits it has in the full call.  B == 0: no launch.
+ *   mhte_can_plan     n must be 6: out = rows per tile, padded d (16: v_mfma_f32_16x16x4_f32, 32:
+ *                     v_mfma_f32_32x32x2_f32), tiles per sample, samples per workgroup, LDS bytes of a workgroup,
+ *                     workspace bytes (0).  Needs no device, a function of (B, F, T, d, layer_num) alone.
+ *   mhte_can_launch_counts: the launches of this process, n must be 2: 0 forward, 1 grad.
+ * activation: 0 identity, 1 relu (the mask of the gradient is h_{i+1} > 0).  Everything is fp32; every product is an
+ * fp32 MFMA; no atomics; the order of every sum is a function of the shape alone: the same bits on every run.  Every
+ * zero written is +0.  No entry point waits for the device, reads a device value or allocates, so a call can be
+ * captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand, a pointer that is not 4-byte aligned, d outside [1, 32], layer_num
+ * outside [1, 8], F < 1, T < 1, F * T beyond 2^30, B < 0 or B >= 2^31, an activation that is neither 0 nor 1, a grad
+ * entry with both outputs NULL. */
+mhte_status mhte_can_forward(const float* user, const float* item, int64_t B, int32_t F, int32_t T, int32_t d,
+                             int32_t layer_num, int32_t activation, float* out, void* stream);
+mhte_status mhte_can_grad(const float* dout, const float* user, const float* item, int64_t B, int32_t F, int32_t T,
+                          int32_t d, int32_t layer_num, int32_t activation, float* duser, float* ditem,
+                          void* stream);
+mhte_status mhte_can_plan(int64_t B, int32_t F, int32_t T, int32_t d, int32_t layer_num, int64_t* out, int32_t n);
+mhte_status mhte_can_launch_counts(int64_t* out, int32_t n);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

@@ -47,6 +47,7 @@
 #include "mhte_fi_kernels.h"
 #include "mhte_cin_kernels.h"
 #include "mhte_dcn_kernels.h"
+#include "mhte_can_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -1976,6 +1977,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_fi_host.h"
 #include "mhte_cin_host.h"
 #include "mhte_dcn_host.h"
+#include "mhte_can_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 #include "mhte_layout_host.h"
@@ -2849,6 +2851,31 @@ mhte_status mhte_dcn_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kDcnCounters) arg_bad(op, "n must be " + std::to_string(kDcnCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kDcnCounters; ++i) out[i] = g_dcn_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- the CAN co-action unit (csrc/mhte_can_core.h, mhte_can_kernels.h, mhte_can_host.h) -----------------
+mhte_status mhte_can_forward(const float* user, const float* item, int64_t B, int32_t F, int32_t T, int32_t d,
+                             int32_t layer_num, int32_t activation, float* out, void* stream) {
+  return guard([&] { can_forward(user, item, B, F, T, d, layer_num, activation, out, stream); });
+}
+
+mhte_status mhte_can_grad(const float* dout, const float* user, const float* item, int64_t B, int32_t F, int32_t T,
+                          int32_t d, int32_t layer_num, int32_t activation, float* duser, float* ditem,
+                          void* stream) {
+  return guard([&] { can_gradient(dout, user, item, B, F, T, d, layer_num, activation, duser, ditem, stream); });
+}
+
+mhte_status mhte_can_plan(int64_t B, int32_t F, int32_t T, int32_t d, int32_t layer_num, int64_t* out, int32_t n) {
+  return guard([&] { can_plan_out(B, F, T, d, layer_num, out, n); });
+}
+
+mhte_status mhte_can_launch_counts(int64_t* out, int32_t n) {
+  return guard([&] {
+    const char* op = "can_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n != kCanCounters) arg_bad(op, "n must be " + std::to_string(kCanCounters) + ", got " + std::to_string(n));
+    for (int i = 0; i < kCanCounters; ++i) out[i] = g_can_launches[i].load(std::memory_order_relaxed);
   });
 }
 

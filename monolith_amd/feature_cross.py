@@ -10,13 +10,19 @@ fp32 MFMA launch per layer forward, two or three backward, without the reference
 ``DCN`` (reference :445-690) is the cross half of a Deep & Cross network, vector and matrix form, over
 ``layer_ops.dcn_cross``: one fused launch per layer forward, and the whole stack is one autograd node whose backward
 carries a single ``dx0`` buffer through the layers.  The ``mixed`` form (low-rank experts), kernel norm and dropout
-are not built.  ``AllInt``, ``CDot`` and ``CAN`` are not built.
+are not built.
+
+``CAN`` (reference :345-440) is the Co-Action Network's unit over ``layer_ops.can_unit``: every sample's item
+embedding is cut into the weights of a small MLP that runs over that sample's user rows; one fused fp32 MFMA launch
+forward and one backward, no intermediate in memory.  Activations None and ``'relu'``; ``'tanh'`` and ``'sigmoid'``,
+``d > 32`` and ``layer_num > 8`` are not built.  ``AllInt`` and ``CDot`` are not built.
 """
 from typing import List, Sequence
 
 import torch
 
-from monolith_amd.layer_ops import CIN_ACTIVATIONS, DCN_TYPES, INT_TYPES, cin_layer, dcn_cross, ffm
+from monolith_amd.layer_ops import (CAN_ACTIVATIONS, CAN_MAX_LAYERS, CIN_ACTIVATIONS, DCN_TYPES, INT_TYPES, can_unit,
+                                    cin_layer, dcn_cross, ffm)
 
 
 class GroupInt(torch.nn.Module):
@@ -200,3 +206,40 @@ class DCN(torch.nn.Module):
             "regularizer": self.regularizer, "num_experts": self.num_experts, "low_rank": self.low_rank,
             "allow_kernel_norm": self.allow_kernel_norm, "use_dropout": self.use_dropout,
             "keep_prob": self.keep_prob, "mode": self.mode}
+
+
+class CAN(torch.nn.Module):
+  """The Co-Action Network's unit (reference :345-440).  The item side is reshaped into the parameters of an MLP,
+  per sample ``layer_num`` pairs ``(W_i [d, d], b_i [d])`` in that order, and the user side is its input:
+  ``h = activation(h @ W_i + b_i)`` on every layer, then the sum over the sequence axis where there is one.  One
+  launch of ``layer_ops.can_unit``'s kernels forward, one backward.
+
+  Args:
+    layer_num: the number of layers, 1 to 8.
+    activation: None or ``'relu'``; ``'tanh'`` and ``'sigmoid'`` are not built.
+    is_seq: the user side has a sequence axis.
+    is_stacked: the user side is several features stacked.
+
+  Input ``(user_emb, item_emb)``: ``user_emb`` ``[B, F, T, d]`` / ``[B, F, d]`` / ``[B, T, d]`` / ``[B, d]`` for
+  (is_seq, is_stacked) = (T, T) / (F, T) / (T, F) / (F, F), ``d <= 32``; ``item_emb`` ``[B, layer_num d (d + 1)]``
+  -> ``[B, F, d]`` when stacked, else ``[B, d]`` (also at ``B = 1``, where the reference's squeeze drops the batch
+  axis).  The layer has no parameters.
+  """
+
+  def __init__(self, layer_num: int = 2, activation="relu", is_seq: bool = False, is_stacked: bool = True):
+    super().__init__()
+    if activation not in CAN_ACTIVATIONS:
+      raise NotImplementedError("CAN: activation must be None or 'relu', got %r" % (activation,))
+    if not isinstance(layer_num, int) or isinstance(layer_num, bool) or not 1 <= layer_num <= CAN_MAX_LAYERS:
+      raise ValueError("CAN: layer_num must be an int in [1, %d], got %r" % (CAN_MAX_LAYERS, layer_num))
+    self.layer_num, self.activation = layer_num, activation
+    self.is_seq, self.is_stacked = bool(is_seq), bool(is_stacked)
+
+  def forward(self, inputs):
+    if not isinstance(inputs, (tuple, list)) or len(inputs) != 2:
+      raise ValueError("CAN: the input must be (user_emb, item_emb)")
+    return can_unit(inputs[0], inputs[1], self.layer_num, self.activation, self.is_seq, self.is_stacked)
+
+  def get_config(self):
+    return {"layer_num": self.layer_num, "activation": self.activation, "is_seq": self.is_seq,
+            "is_stacked": self.is_stacked}

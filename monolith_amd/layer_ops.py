@@ -24,6 +24,11 @@ vector and matrix forms) behind ``mhte_dcn_layer`` / ``mhte_dcn_layer_grad`` (cs
 launch whose epilogue does the bias, the multiply by ``x0`` and the residual, and a gradient that carries the stack's
 running ``dx0`` as an operand.
 
+``can_unit`` is the Co-Action Network's unit (feature_cross.py:345-440, ``feature_cross.CAN``) behind
+``mhte_can_forward`` / ``mhte_can_grad`` (csrc/mhte_can_kernels.h): every sample's own small MLP, cut out of its item
+embedding, runs over its user rows as a chain of fp32 MFMAs that never leaves the registers; one launch forward, one
+backward, nothing saved but the two inputs.
+
 Tensors are float32 on the GPU; a tensor that is not contiguous is copied first.
 """
 import ctypes as C
@@ -550,3 +555,119 @@ def dcn_launch_counts():
   out = (C.c_int64 * len(DCN_COUNTER_NAMES))()
   check(_lib.lib().mhte_dcn_launch_counts(out, len(DCN_COUNTER_NAMES)))
   return dict(zip(DCN_COUNTER_NAMES, [int(x) for x in out]))
+
+
+# ---- the CAN co-action unit (feature_cross.py:345-440) ------------------------------------------------------------
+CAN_ACTIVATIONS = (None, "relu")   # the index is the ABI's activation; the reference's 'tanh' / 'sigmoid' are not built
+CAN_MAX_DIM, CAN_MAX_LAYERS = 32, 8
+CAN_COUNTER_NAMES = ("forward", "grad")   # mhte_can_launch_counts' order
+# mhte_can_plan's order
+CAN_PLAN_NAMES = ("rows_per_tile", "padded_d", "tiles_per_sample", "samples_per_workgroup", "lds_bytes",
+                  "workspace_bytes")
+
+
+def _can_dims(what, user, item, layer_num, activation, is_seq, is_stacked):
+  """-> (B, F, T, d, the ABI's activation, {name: the shape it must have}); every refusal that needs no device."""
+  if activation not in CAN_ACTIVATIONS:
+    raise NotImplementedError("%s: activation must be None or 'relu', got %r" % (what, activation))
+  if not isinstance(layer_num, int) or isinstance(layer_num, bool) or not 1 <= layer_num <= CAN_MAX_LAYERS:
+    raise ValueError("%s: layer_num must be an int in [1, %d], got %r" % (what, CAN_MAX_LAYERS, layer_num))
+  for name, t in (("user", user), ("item", item)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError("%s: %s must be a torch tensor, got %s" % (what, name, type(t).__name__))
+  rank = 2 + bool(is_seq) + bool(is_stacked)
+  if user.dim() != rank:
+    raise ValueError("%s: user must be %dD for is_seq=%s, is_stacked=%s (shape %s)"
+                     % (what, rank, bool(is_seq), bool(is_stacked), tuple(user.shape)))
+  if item.dim() != 2:
+    raise ValueError("%s: item is not 2D (shape %s)" % (what, tuple(item.shape)))
+  B, d = int(user.shape[0]), int(user.shape[-1])
+  F = int(user.shape[1]) if is_stacked else 1
+  T = int(user.shape[-2]) if is_seq else 1
+  if not 1 <= d <= CAN_MAX_DIM:
+    raise ValueError("%s: d must be in [1, %d], got %d" % (what, CAN_MAX_DIM, d))
+  if F < 1 or T < 1:
+    raise ValueError("%s: F and T must be >= 1, got user of shape %s" % (what, tuple(user.shape)))
+  if int(item.shape[0]) != B:
+    raise ValueError("%s: user has B = %d, item B = %d" % (what, B, int(item.shape[0])))
+  P = layer_num * d * (d + 1)
+  if int(item.shape[1]) != P:
+    raise ValueError("%s: item must be layer_num * d * (d + 1) = %d wide, got %d" % (what, P, int(item.shape[1])))
+  res = (B, F, d) if is_stacked else (B, d)
+  return B, F, T, d, CAN_ACTIVATIONS.index(activation), {"user": tuple(user.shape), "item": (B, P), "dout": res}
+
+
+def can_forward(user: torch.Tensor, item: torch.Tensor, layer_num: int = 2, activation="relu", is_seq: bool = False,
+                is_stacked: bool = True) -> torch.Tensor:
+  """CAN.call (feature_cross.py:386-430), no autograd: ``user`` ``[B, F, T, d]`` (stacked sequence), ``[B, F, d]``
+  (stacked), ``[B, T, d]`` (sequence) or ``[B, d]``, ``item`` ``[B, layer_num d (d + 1)]`` -> ``[B, F, d]`` (stacked)
+  or ``[B, d]`` (always, also at ``B = 1``).  ``h = act(h @ W_i + b_i)`` on every layer with sample b's ``W_i``,
+  ``b_i`` cut out of ``item[b]``, then the sum over ``T``.  One launch; ``activation`` None or ``'relu'`` (``'tanh'``
+  and ``'sigmoid'`` are not built), ``1 <= d <= 32``, ``1 <= layer_num <= 8``; ``B = 0`` returns an empty result
+  without a launch."""
+  what = "can_forward"
+  B, F, T, d, act, shapes = _can_dims(what, user, item, layer_num, activation, is_seq, is_stacked)
+  user, item = _cin_operands(what, shapes, user=user, item=item)
+  out = torch.empty(shapes["dout"], dtype=torch.float32, device=user.device)
+  if B:
+    with torch.cuda.device(user.device):
+      check(_lib.lib().mhte_can_forward(vp(user), vp(item), B, F, T, d, layer_num, act, vp(out), _stream()))
+  return out
+
+
+def can_grad(dout: torch.Tensor, user: torch.Tensor, item: torch.Tensor, layer_num: int = 2, activation="relu",
+             is_seq: bool = False, is_stacked: bool = True, want_user: bool = True, want_item: bool = True):
+  """-> (duser, ditem) of ``can_forward``, shaped like ``user`` and ``item``, in one launch that recomputes the
+  layers (nothing of the forward is needed).  A gradient that is not wanted is None; asking for one alone gives the
+  same bits as asking for both."""
+  what = "can_grad"
+  if not (want_user or want_item):
+    raise ValueError("%s: at least one of want_user and want_item" % what)
+  B, F, T, d, act, shapes = _can_dims(what, user, item, layer_num, activation, is_seq, is_stacked)
+  dout, user, item = _cin_operands(what, shapes, dout=dout, user=user, item=item)
+  duser = torch.empty_like(user) if want_user else None
+  ditem = torch.empty_like(item) if want_item else None
+  if B:
+    with torch.cuda.device(user.device):
+      check(_lib.lib().mhte_can_grad(vp(dout), vp(user), vp(item), B, F, T, d, layer_num, act, vp(duser), vp(ditem),
+                                     _stream()))
+  return duser, ditem
+
+
+class _CanUnit(torch.autograd.Function):
+  """CAN.call as one node: one launch forward, one backward; saves its two inputs and nothing else."""
+
+  @staticmethod
+  def forward(ctx, user, item, layer_num, activation, is_seq, is_stacked):
+    ctx.save_for_backward(user, item)
+    ctx.form = (layer_num, activation, is_seq, is_stacked)
+    return can_forward(user, item, layer_num, activation, is_seq, is_stacked)
+
+  @staticmethod
+  def backward(ctx, g):
+    user, item = ctx.saved_tensors
+    want = ctx.needs_input_grad[:2]
+    duser, ditem = can_grad(g, user, item, *ctx.form, want_user=want[0], want_item=want[1])
+    return duser, ditem, None, None, None, None
+
+
+def can_unit(user: torch.Tensor, item: torch.Tensor, layer_num: int = 2, activation="relu", is_seq: bool = False,
+             is_stacked: bool = True) -> torch.Tensor:
+  """``can_forward``, differentiable in ``user`` and ``item`` as ONE autograd node: one launch forward, one backward,
+  no torch arithmetic; the node saves its two inputs only.  Under ``torch.no_grad()`` the forward alone runs."""
+  return _CanUnit.apply(user, item, layer_num, activation, bool(is_seq), bool(is_stacked))
+
+
+def can_plan(B: int, F: int, T: int, d: int, layer_num: int):
+  """{rows_per_tile, padded_d, tiles_per_sample, samples_per_workgroup, lds_bytes, workspace_bytes} of a call
+  (mhte_can_plan): a function of the shape alone, no device needed."""
+  out = (C.c_int64 * len(CAN_PLAN_NAMES))()
+  check(_lib.lib().mhte_can_plan(int(B), int(F), int(T), int(d), int(layer_num), out, len(CAN_PLAN_NAMES)))
+  return dict(zip(CAN_PLAN_NAMES, [int(x) for x in out]))
+
+
+def can_launch_counts():
+  """{kernel: launches of this process} (mhte_can_launch_counts)."""
+  out = (C.c_int64 * len(CAN_COUNTER_NAMES))()
+  check(_lib.lib().mhte_can_launch_counts(out, len(CAN_COUNTER_NAMES)))
+  return dict(zip(CAN_COUNTER_NAMES, [int(x) for x in out]))
