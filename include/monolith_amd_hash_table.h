@@ -779,6 +779,42 @@ mhte_status mhte_can_grad(const float* dout, const float* user, const float* ite
 mhte_status mhte_can_plan(int64_t B, int32_t F, int32_t T, int32_t d, int32_t layer_num, int64_t* out, int32_t n);
 mhte_status mhte_can_launch_counts(int64_t* out, int32_t n);
 
+/* ---- AutoInt (csrc/mhte_autoint_core.h, mhte_autoint_kernels.h, mhte_autoint_host.h) ------------------------
+ * The parameter-free self-attention stack over a sample's fields (NT/layers/feature_trans.py:31-93, AutoInt.call).
+ * x, out, dout, dx [dev f32, B x n x k]; states [dev f32, (layer_num - 1) x B x n x k].  Per sample, X_0 = x[b] and
+ * per layer l < layer_num:
+ *   S = X_l X_l^T [n x n]      P = softmax(S, axis = -1)      X_{l+1} = P X_l          out[b] = X_layer_num
+ *   mhte_autoint_forward  replaces :71-80 (per layer a batched matmul, a softmax and a batched matmul, with two
+ *                         [B x n x n] round trips through memory): one launch for the whole stack, a workgroup per
+ *                         sample, S and P in registers only.  states, when not NULL and layer_num > 1, receives
+ *                         X_1 .. X_{layer_num - 1} for the gradient; out has the same bits with and without it.
+ *                         states may be NULL: not wanted, or layer_num == 1.  B == 0: no launch.
+ *   mhte_autoint_grad     replaces the autograd backward of those lines: one launch that walks the layers last to
+ *                         first with X_l from x / states,
+ *                           dP = dO X^T    delta_i = dO_i . X_{l+1, i} = sum_j P_ij dP_ij
+ *                           dS = P * (dP - delta)    dX = (dS + dS^T) X + P^T dO
+ *                         and writes dx.  delta is taken in its second form (exactly dP_ii where the softmax
+ *                         saturates), so out is checked like an operand and not read.  states is NULL if and only
+ *                         if layer_num == 1.  B == 0: no launch.
+ *   mhte_autoint_plan     n_out must be 7: out = tile (16: v_mfma_f32_16x16x4_f32 for n <= 16, else 32:
+ *                         v_mfma_f32_32x32x2_f32), row tiles (the wavefronts of a workgroup), padded k, samples per
+ *                         workgroup (1), LDS bytes of the forward, LDS bytes of the gradient (both at most 163840),
+ *                         workspace bytes (0).  Needs no device, a function of (B, n, k, layer_num) alone.
+ *   mhte_autoint_launch_counts: the launches of this process, n_out must be 2: 0 forward, 1 grad.
+ * Everything is fp32; every product is an fp32 MFMA; the softmax subtracts the row maximum (exact two-pass); no
+ * atomics; the order of every sum is a function of the shape alone: the same bits on every run.  No entry point
+ * waits for the device, reads a device value or allocates, so a call can be captured into a graph.
+ * InvalidArgument, checked on the host before any device call, the entry point's name and the argument in the
+ * message: a null pointer for a non-empty operand, a pointer that is not 4-byte aligned, n outside [1, 128], k
+ * outside [1, 64], layer_num outside [1, 8], B < 0 or B >= 2^31, states given to the grad entry at layer_num == 1.
+ * Not built: multi-head or projected attention (the reference has neither), bf16, n > 128, k > 64. */
+mhte_status mhte_autoint_forward(const float* x, int64_t B, int32_t n, int32_t k, int32_t layer_num, float* out,
+                                 float* states, void* stream);
+mhte_status mhte_autoint_grad(const float* dout, const float* x, const float* states, const float* out, int64_t B,
+                              int32_t n, int32_t k, int32_t layer_num, float* dx, void* stream);
+mhte_status mhte_autoint_plan(int64_t B, int32_t n, int32_t k, int32_t layer_num, int64_t* out, int32_t n_out);
+mhte_status mhte_autoint_launch_counts(int64_t* out, int32_t n_out);
+
 /* ---- split by indices (csrc/mhte_split_kernels.h, mhte_split_host.h) -------------------------------------
  * MonolithSplitByIndices, MonolithSplitByIndicesGradient and MonolithRaggedSplitByIndices
  * (RT/ops/split_by_indices_op.cc:28-75, :77-118, :188-243; Python NT/distribution_ops.py:27-78), the shard split

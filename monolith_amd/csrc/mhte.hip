@@ -48,6 +48,7 @@
 #include "mhte_cin_kernels.h"
 #include "mhte_dcn_kernels.h"
 #include "mhte_can_kernels.h"
+#include "mhte_autoint_kernels.h"
 #include "mhte_group_kernels.h"
 #include "mhte_split_kernels.h"
 #include "mhte_sharding_kernels.h"
@@ -1978,6 +1979,7 @@ static void ragged_upsert(mhte_multi_table* t, const int64_t* id, const int64_t*
 #include "mhte_cin_host.h"
 #include "mhte_dcn_host.h"
 #include "mhte_can_host.h"
+#include "mhte_autoint_host.h"
 #include "mhte_split_host.h"
 #include "mhte_sharding_host.h"
 #include "mhte_layout_host.h"
@@ -2876,6 +2878,31 @@ mhte_status mhte_can_launch_counts(int64_t* out, int32_t n) {
     if (!out) arg_bad(op, "null argument: out");
     if (n != kCanCounters) arg_bad(op, "n must be " + std::to_string(kCanCounters) + ", got " + std::to_string(n));
     for (int i = 0; i < kCanCounters; ++i) out[i] = g_can_launches[i].load(std::memory_order_relaxed);
+  });
+}
+
+// ---- AutoInt (csrc/mhte_autoint_core.h, mhte_autoint_kernels.h, mhte_autoint_host.h) --------------------
+mhte_status mhte_autoint_forward(const float* x, int64_t B, int32_t n, int32_t k, int32_t layer_num, float* out,
+                                 float* states, void* stream) {
+  return guard([&] { autoint_forward(x, B, n, k, layer_num, out, states, stream); });
+}
+
+mhte_status mhte_autoint_grad(const float* dout, const float* x, const float* states, const float* out, int64_t B,
+                              int32_t n, int32_t k, int32_t layer_num, float* dx, void* stream) {
+  return guard([&] { autoint_gradient(dout, x, states, out, B, n, k, layer_num, dx, stream); });
+}
+
+mhte_status mhte_autoint_plan(int64_t B, int32_t n, int32_t k, int32_t layer_num, int64_t* out, int32_t n_out) {
+  return guard([&] { autoint_plan_out(B, n, k, layer_num, out, n_out); });
+}
+
+mhte_status mhte_autoint_launch_counts(int64_t* out, int32_t n_out) {
+  return guard([&] {
+    const char* op = "autoint_launch_counts";
+    if (!out) arg_bad(op, "null argument: out");
+    if (n_out != kAutoIntCounters)
+      arg_bad(op, "n_out must be " + std::to_string(kAutoIntCounters) + ", got " + std::to_string(n_out));
+    for (int i = 0; i < kAutoIntCounters; ++i) out[i] = g_autoint_launches[i].load(std::memory_order_relaxed);
   });
 }
 

@@ -29,6 +29,10 @@ running ``dx0`` as an operand.
 embedding, runs over its user rows as a chain of fp32 MFMAs that never leaves the registers; one launch forward, one
 backward, nothing saved but the two inputs.
 
+``autoint`` is the self-attention stack of AutoInt (feature_trans.py:31-93, ``feature_trans.AutoInt``) behind
+``mhte_autoint_forward`` / ``mhte_autoint_grad`` (csrc/mhte_autoint_kernels.h): a workgroup per sample keeps the state
+in LDS through all layers, the scores and the softmax in registers; one launch forward, one backward.
+
 Tensors are float32 on the GPU; a tensor that is not contiguous is copied first.
 """
 import ctypes as C
@@ -671,3 +675,105 @@ def can_launch_counts():
   out = (C.c_int64 * len(CAN_COUNTER_NAMES))()
   check(_lib.lib().mhte_can_launch_counts(out, len(CAN_COUNTER_NAMES)))
   return dict(zip(CAN_COUNTER_NAMES, [int(x) for x in out]))
+
+
+# ---- AutoInt (feature_trans.py:31-93) -------------------------------------------------------------------------------
+AUTOINT_MAX_N, AUTOINT_MAX_K, AUTOINT_MAX_LAYERS = 128, 64, 8
+AUTOINT_COUNTER_NAMES = ("forward", "grad")   # mhte_autoint_launch_counts' order
+# mhte_autoint_plan's order
+AUTOINT_PLAN_NAMES = ("tile", "row_tiles", "padded_k", "samples_per_workgroup", "lds_bytes_forward", "lds_bytes_grad",
+                      "workspace_bytes")
+
+
+def _autoint_dims(what, x, layer_num):
+  """-> (B, n, k); every refusal that needs no device."""
+  if not isinstance(layer_num, int) or isinstance(layer_num, bool) or not 1 <= layer_num <= AUTOINT_MAX_LAYERS:
+    raise ValueError("%s: layer_num must be an int in [1, %d], got %r" % (what, AUTOINT_MAX_LAYERS, layer_num))
+  if not isinstance(x, torch.Tensor):
+    raise TypeError("%s: x must be a torch tensor, got %s" % (what, type(x).__name__))
+  if x.dim() != 3:
+    raise ValueError("%s: x is not 3D (shape %s)" % (what, tuple(x.shape)))
+  B, n, k = (int(s) for s in x.shape)
+  if not 1 <= n <= AUTOINT_MAX_N:
+    raise ValueError("%s: n must be in [1, %d], got %d" % (what, AUTOINT_MAX_N, n))
+  if not 1 <= k <= AUTOINT_MAX_K:
+    raise ValueError("%s: k must be in [1, %d], got %d" % (what, AUTOINT_MAX_K, k))
+  return B, n, k
+
+
+def autoint_forward(x: torch.Tensor, layer_num: int = 1, want_states: bool = False):
+  """AutoInt.call's loop (feature_trans.py:71-80), no autograd: ``x`` ``[B, n, k]`` -> ``(out [B, n, k], states)``.
+  Per layer ``X <- softmax(X X^T, -1) X``, the whole stack in one launch.  ``states`` is ``[layer_num - 1, B, n, k]``
+  (``X_1 .. X_{L-1}``, what ``autoint_grad`` needs) when ``want_states`` and ``layer_num > 1``, else None; ``out`` has
+  the same bits either way.  ``1 <= n <= 128``, ``1 <= k <= 64``, ``1 <= layer_num <= 8``; ``B = 0`` returns an empty
+  result without a launch."""
+  what = "autoint_forward"
+  B, n, k = _autoint_dims(what, x, layer_num)
+  x, = _cin_operands(what, {}, x=x)
+  out = torch.empty_like(x)
+  states = None
+  if want_states and layer_num > 1:
+    states = torch.empty((layer_num - 1, B, n, k), dtype=torch.float32, device=x.device)
+  if B:
+    with torch.cuda.device(x.device):
+      check(_lib.lib().mhte_autoint_forward(vp(x), B, n, k, layer_num, vp(out), vp(states), _stream()))
+  return out, states
+
+
+def autoint_grad(dout: torch.Tensor, x: torch.Tensor, states: Optional[torch.Tensor], out: torch.Tensor,
+                 layer_num: int = 1) -> torch.Tensor:
+  """-> dx of ``autoint_forward`` in one launch that walks the layers last to first; ``states`` and ``out`` are the
+  forward's (``states`` None exactly when ``layer_num == 1``).  ``out`` is checked like an operand and not read:
+  the kernel takes ``delta_i = dO_i . O_i`` as ``sum_j P_ij dP_ij``, which is exactly ``dP_ii`` where the softmax
+  saturates."""
+  what = "autoint_grad"
+  B, n, k = _autoint_dims(what, x, layer_num)
+  if (states is None) != (layer_num == 1):
+    raise ValueError("%s: states must be None exactly when layer_num == 1 (layer_num = %d)" % (what, layer_num))
+  shapes = {"dout": (B, n, k), "out": (B, n, k), "states": (layer_num - 1, B, n, k)}
+  dout, x, states, out = _cin_operands(what, shapes, dout=dout, x=x, states=states, out=out)
+  dx = torch.empty_like(x)
+  if B:
+    with torch.cuda.device(x.device):
+      check(_lib.lib().mhte_autoint_grad(vp(dout), vp(x), vp(states), vp(out), B, n, k, layer_num, vp(dx), _stream()))
+  return dx
+
+
+class _AutoInt(torch.autograd.Function):
+  """The whole stack as one node: one launch forward, one backward; saves x, the states and out."""
+
+  @staticmethod
+  def forward(ctx, x, layer_num):
+    out, states = autoint_forward(x, layer_num, want_states=True)
+    ctx.layer_num = layer_num
+    ctx.save_for_backward(*((x, out) if states is None else (x, out, states)))
+    return out
+
+  @staticmethod
+  def backward(ctx, g):
+    x, out, *states = ctx.saved_tensors
+    return autoint_grad(g, x, states[0] if states else None, out, ctx.layer_num), None
+
+
+def autoint(x: torch.Tensor, layer_num: int = 1) -> torch.Tensor:
+  """``autoint_forward``'s ``out``, differentiable in ``x`` as ONE autograd node for the whole stack: one launch
+  forward, one backward, no torch arithmetic.  Under ``torch.no_grad()``, or when ``x`` needs no gradient, no states
+  buffer is passed; otherwise the node saves ``x``, ``states`` and ``out``."""
+  if isinstance(x, torch.Tensor) and not (torch.is_grad_enabled() and x.requires_grad):
+    return autoint_forward(x, layer_num)[0]
+  return _AutoInt.apply(x, layer_num)
+
+
+def autoint_plan(B: int, n: int, k: int, layer_num: int):
+  """{tile, row_tiles, padded_k, samples_per_workgroup, lds_bytes_forward, lds_bytes_grad, workspace_bytes} of a call
+  (mhte_autoint_plan): a function of the shape alone, no device needed."""
+  out = (C.c_int64 * len(AUTOINT_PLAN_NAMES))()
+  check(_lib.lib().mhte_autoint_plan(int(B), int(n), int(k), int(layer_num), out, len(AUTOINT_PLAN_NAMES)))
+  return dict(zip(AUTOINT_PLAN_NAMES, [int(v) for v in out]))
+
+
+def autoint_launch_counts():
+  """{kernel: launches of this process} (mhte_autoint_launch_counts)."""
+  out = (C.c_int64 * len(AUTOINT_COUNTER_NAMES))()
+  check(_lib.lib().mhte_autoint_launch_counts(out, len(AUTOINT_COUNTER_NAMES)))
+  return dict(zip(AUTOINT_COUNTER_NAMES, [int(v) for v in out]))
